@@ -1,7 +1,16 @@
 """Benchmark: batched madigan market-simulation step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--fuse F] [--n-envs 8192]
-                    [--workload C3|C2|C4|C5]
+                    [--workload C3|C2|C4|C5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(value, ms_per_step, the configuration).  `--dump-outputs DIR` also writes the
+last timed step's outputs to DIR/<name>.npy, for comparing two builds.
+`--full` adds everything that takes runs of its own after the timed region:
+the step kernel's own duration and the roofline block priced on it, the
+bandwidth probe, the episode-age and launch-length blocks, the zero-copy
+window form of the windowed workloads and the CPU baseline (each still
+switched off by its --no-... option).
 
 Workload (BASELINE.json configs[2], SURVEY 8d "C3"): 8192 envs x 8 assets per
 GPU, TrendOU generators (config.yaml:116-138), Broker with 1e-4 relative
@@ -124,6 +133,34 @@ def bandwidth_probe(dev, nbytes: int = 2 << 30, reps: int = 10):
                                     C.byref(out)))
     del src, dst
     return out.value
+
+
+DUMP_BUDGET = 64_000_000  # bytes of --dump-outputs files in all
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: `arrays` (name -> tensor or array, env-major) as
+    path/<name>.npy, float64 where the output is 64 bits wide (integers
+    included), else float32.  Above DUMP_BUDGET bytes in all, the same fixed,
+    seeded sample of envs of every array (its indices: env_index.npy)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v)) for k, v in arrays.items()}
+    kinds = {k: np.float64 if v.element_size() > 2 else np.float32 for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    per_env = sum(v[0].numel() * np.dtype(kinds[k]).itemsize for k, v in arrays.items())
+    budget = DUMP_BUDGET - 256 * (len(arrays) + 1)  # (.npy headers)
+    info = {"dir": path, "envs": n, "sampled": False}
+    if n * per_env > budget:
+        m = max(1, budget // (per_env + 8))
+        idx = np.sort(np.random.default_rng(0x6D6164).choice(n, m, replace=False))
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+        arrays = {k: v[torch.as_tensor(idx, device=v.device)] for k, v in arrays.items()}
+        info.update(envs=int(m), sampled=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v.cpu().numpy().astype(kinds[k]))
+    info["files"] = sorted(list(arrays) + (["env_index"] if info["sampled"] else []))
+    return info
 
 
 SCHED_NAMES = {1: "single", 2: "duo", 3: "trio"}
@@ -447,9 +484,17 @@ def main():
     ap.add_argument("--k1-hist", dest="k1_ring", action="store_false",
                     help="windowed workloads at --win-fuse 1: the launch-history path (mgn_rollout_hist + "
                          "mgn_window_hist) instead of mgn_rollout + mgn_window")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what takes runs of its own: the step "
+                         "kernel's duration and the roofline block, the bandwidth probe, the episode-age "
+                         "and launch-length blocks, the windowed workloads' zero-copy form, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs (what the timed path's caller "
+                         "receives for that step) as DIR/<name>.npy, float32 / float64, at most 64 MB in "
+                         "all (above that a fixed, seeded sample of envs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-k-sweep", dest="k_sweep", action="store_false",
-                    help="skip the K = 1 / 16 / 256 launch-length block of the line")
+                    help="--full: skip the K = 1 / 16 / 256 launch-length block of the line")
     ap.add_argument("--sweep", action="store_true",
                     help="also time 1/16/64/256 steps per launch (separate launches; keep it off "
                          "when profiling, so the kernel's rocprof average is the headline's)")
@@ -521,12 +566,11 @@ def main():
         from madigan_amd import _lib as L
         L.check(env.lib.mgn_set_schedule(env.h, {"single": L.SCHED_SINGLE, "duo": L.SCHED_DUO,
                                                   "trio": L.SCHED_TRIO}[args.schedule]), env.h)
-    import ctypes as C
     from madigan_amd import _lib as L
     lib, h = env.lib, env.h
     total = args.warmup + args.steps
-    # rows [total, total + steps): the kernel-timing launches after the timed
-    # region (the same launch plan on the next rows)
+    # rows [total, total + steps): --full's kernel-timing launches after the
+    # timed region (the same launch plan on the next rows)
     actions = env.generate_actions(total + args.steps, seed=0x6D6164)
     traj = env.alloc_traj(F, fields=[f for f in ("reward", "shaped", "done", "obs_price", "obs_port",
                                                  "timestamp", "tprice", "tunits", "tcost", "risk",
@@ -570,15 +614,16 @@ def main():
         return rc
 
     warm, timed = plan(0, args.warmup), plan(args.warmup, total)
-    probe_plan = plan(total, total + args.steps)
+    probe_plan = plan(total, total + args.steps) if args.full else []
     # the handle's stream (every launch is on it); --wait spin polls it
     sync = env.stream_synchronizer(spin=args.wait == "spin")
-    # kernel durations: HIP events around each step launch on the handle's
-    # stream (mgn_set_timing; pooled events, created during the warmup) -- on
-    # the kernel-timing launches after the timed region only: the timed
-    # region issues the product path exactly as a caller does, with no events
+    # kernel durations (--full): HIP events around each step launch on the
+    # handle's stream (mgn_set_timing; pooled events, created during the
+    # warmup) -- on the kernel-timing launches after the timed region only: the
+    # timed region issues the product path exactly as a caller does, with no events
     tmode = 2 if args.timing == "launch" else 1
-    L.check(lib.mgn_set_timing(h, tmode), h)
+    if args.full:
+        L.check(lib.mgn_set_timing(h, tmode), h)
     L.check(run(warm, "warmup"), h)
     torch.cuda.synchronize()
     L.check(lib.mgn_set_timing(h, 0), h)
@@ -596,6 +641,12 @@ def main():
     elapsed = time.perf_counter() - t0
     torch.cuda.synchronize()
     L.check(rc, h)
+    last = None
+    if rank == 0 and args.dump_outputs and timed:
+        # the last timed step: the last row of the last timed launch's
+        # trajectory (copied now: --full's launches reuse the trajectory)
+        n_last = timed[-1][2]
+        last = {k: v[n_last - 1].clone() for k, v in outs[n_last].items()}
     # the sharded path's one collective, issued at log intervals
     # in a training loop, not per step: after the timed steps, timed on its own
     from madigan_amd import distributed as D
@@ -610,6 +661,61 @@ def main():
             t = t.cpu()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    value = world * N * args.steps / elapsed
+    episodes = int(gathered[:, 3].sum().item())
+    steps_per_launch = args.steps / max(len(timed), 1)
+    dumped = dump_outputs(args.dump_outputs, last) if last is not None else None
+    del last
+    if rank == 0:
+        res = {
+            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": "C3: TrendOU x8 assets per env, slippage 1e-4 + 2% cost broker, "
+                                   + (f"DDR eta=.001 n={args.nstep} (discount .99, {args.nstep_pop} pop; "
+                                      "a diagnostic line, not the headline)" if args.nstep > 1 else
+                                      "DDR eta=.001 n=1")
+                                   + ", discrete actions via action_to_transaction, auto-reset",
+                       "nstep": args.nstep, "nstep_pop": args.nstep_pop if args.nstep > 1 else None,
+                       "n_envs_per_gpu": N, "n_envs_total": world * N, "n_assets": A, "window": 0,
+                       "steps_per_launch": steps_per_launch,
+                       "assets_per_lane": int(lib.mgn_get_layout(h)),
+                       "schedule": SCHED_NAMES[int(lib.mgn_get_schedule(h))],
+                       "parallelism": f"env-sharded x{world} (no per-step collective)"
+                                      + (f", {args.dist_backend}" if world > 1 else "")},
+            "timed_region_us_per_launch": elapsed * 1e6 / max(len(timed), 1),
+            "episodes_completed": episodes,
+            "stats_allgather_us": allgather_us,
+            "allgather_path": allgather_path,
+        }
+        if dumped:
+            res["dumped_outputs"] = dumped
+    if rank == 0 and args.dump_stats:
+        np.save(args.dump_stats, gathered.cpu().numpy())
+    if args.full:
+        more = c3_full(args, env, dev, rank, world, run, sync, probe_plan, logl, traj, total)
+        if rank == 0:
+            res.update(more)
+    if rank == 0:
+        res["launch_log"] = launch_log
+        print(json.dumps(res))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def c3_full(args, env, dev, rank, world, run, sync, probe_plan, logl, traj, total):
+    """--full, after C3's timed region (every rank runs the kernel-timing
+    launches, rank 0 the rest): the step kernel's own duration and the roofline
+    block priced on it, the episode-age and launch-length blocks, the
+    bandwidth probe and the CPU baseline; rank 0 returns the line's further
+    entries."""
+    import ctypes as C
+    import torch
+    from madigan_amd import _lib as L
+    lib, h = env.lib, env.h
+    N, A = args.n_envs, args.assets
+    tmode = 2 if args.timing == "launch" else 1
     # the step kernel's duration: the timed region's launch plan once more,
     # right after it, on the next action rows, with the launches' own events
     L.check(lib.mgn_set_timing(h, tmode), h)
@@ -628,8 +734,6 @@ def main():
     bpes = survey_bytes_per_env_step(env)
     achieved_gbs = units_per_launch * bpes / avg_launch_s / 1e9
     fused = bytes_per_env_step(A, steps_per_launch, env.D)
-    value = world * N * args.steps / elapsed
-    episodes = int(gathered[:, 3].sum().item())
     age = total + args.steps  # steps the handle has run
 
     # after the timed region, rank 0 only: the same handle continues on fresh
@@ -734,8 +838,7 @@ def main():
         ages[str(tgt)] = at_age(tgt)
         del sw_fns, sw_traj, sw_actions
 
-    if rank == 0 and args.dump_stats:
-        np.save(args.dump_stats, gathered.cpu().numpy())
+    res = {}
     if rank == 0:
         K = int(round(steps_per_launch))
         # (n-step handles have PMC entries of their own: the pops' rows)
@@ -785,25 +888,8 @@ def main():
             roof["attainable_GBs"] = max(probe, GUIDE_COPY_GBS)
             roof["frac_of_attainable"] = achieved_gbs / roof["attainable_GBs"]
         res = {
-            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "C3: TrendOU x8 assets per env, slippage 1e-4 + 2% cost broker, "
-                                   + (f"DDR eta=.001 n={args.nstep} (discount .99, {args.nstep_pop} pop; "
-                                      "a diagnostic line, not the headline)" if args.nstep > 1 else
-                                      "DDR eta=.001 n=1")
-                                   + ", discrete actions via action_to_transaction, auto-reset",
-                       "nstep": args.nstep, "nstep_pop": args.nstep_pop if args.nstep > 1 else None,
-                       "n_envs_per_gpu": N, "n_envs_total": world * N, "n_assets": A, "window": 0,
-                       "steps_per_launch": steps_per_launch,
-                       "assets_per_lane": int(lib.mgn_get_layout(h)),
-                       "schedule": SCHED_NAMES[int(lib.mgn_get_schedule(h))],
-                       "parallelism": f"env-sharded x{world} (no per-step collective)"
-                                      + (f", {args.dist_backend}" if world > 1 else "")},
             "roofline": roof,
             "kernel_us_per_step": avg_launch_s * 1e6 / steps_per_launch,
-            "timed_region_us_per_launch": elapsed * 1e6 / max(n_launch, 1),
             "kernel_timing": {
                 "launches": n_launch, "avg_launch_us": avg_launch_s * 1e6,
                 "region_us_with_events": probe_s * 1e6,
@@ -811,9 +897,6 @@ def main():
                         "figure (roofline.avg_launch_us) comes from the same launch plan issued right "
                         "after it on the next action rows, each launch recording its own HIP events "
                         "(region_us_with_events: that plan's wall time, events included)"},
-            "episodes_completed": episodes,
-            "stats_allgather_us": allgather_us,
-            "allgather_path": allgather_path,
         }
         if steady:
             res["steady_state"] = steady
@@ -822,7 +905,6 @@ def main():
                 "the headline's launch on the same handle after the timed region, at the handle's step "
                 "index age_steps (fresh actions): kernel time from the launch's own HIP events; the "
                 "steady-state figure is the one after >= 2000 untimed steps (episodes ended)")
-        res["launch_log"] = launch_log
         if sweep:
             res["launch_lengths"] = sweep
             res["launch_lengths_note"] = (
@@ -832,9 +914,7 @@ def main():
                 "dispatch included); frac on SURVEY 8d bytes (1393 B per C3 env-step) over the kernel time")
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(N, A, args.cpu_budget)
-        print(json.dumps(res))
-    if world > 1:
-        dist.destroy_process_group()
+    return res
 
 
 def c1_latency(args, world, rank, dev):
@@ -860,16 +940,27 @@ def c1_latency(args, world, rank, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for t in range(T):
-        env.step(units[200 + t])
+        ret = env.step(units[200 + t])
     torch.cuda.synchronize()
     us = (time.perf_counter() - t0) / T * 1e6
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's return, as (1, ...) arrays (one env)
+        state, reward, done, info = ret
+        br = info.brokerResponse
+        dumped = dump_outputs(args.dump_outputs, {k: np.asarray(v, dtype=np.float64).reshape(1, -1) for k, v in (
+            ("price", state.price), ("portfolio", state.portfolio), ("reward", reward), ("done", done),
+            ("transactionPrice", br.transactionPrice), ("transactionUnits", br.transactionUnits),
+            ("transactionCost", br.transactionCost))})
     res = {"metric": "Env.step latency (C1: 1 env x 1 asset, Python per-step call)", "value": us,
            "unit": "us/step", "n_gpus": 1, "steps": T, "warmup": 200, "ms_per_step": us / 1e3,
            "higher_is_better": False, "scaling": "none", "vs_baseline": None, "dtype": "f64",
            "data": "synthetic",
            "config": {"workload": "C1: Synth sine freq 1 mu 2 amp 1 phase 0 dX .01 noise 0, no costs, "
                                   "env log reward, Env.step(units) from Python"}}
-    if not args.no_cpu_baseline:
+    if dumped:
+        res["dumped_outputs"] = dumped
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         from oracle import oracle as O
         orc = O.OracleBatch(dict(n_envs=1, seed=0x6D6165), [(O.SRC_SINE, [1.0, 2.0, 1.0, 0.0, 0.01, 0.0])])
@@ -980,8 +1071,14 @@ def windowed(args, world, rank, dev):
     # the same launches with the windows read in place from the launch
     # history (mgn_window_hist_view) instead of materialised -- measured after
     # the timed region, reported beside the line, never as its value
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the last timed step: the last row of the launch's trajectory and windows
+        dumped = dump_outputs(args.dump_outputs, {
+            **{k: v[Kf - 1] for k, v in traj.items()},
+            "window_price": wp[Kf - 1], "window_portfolio": wo[Kf - 1], "window_timestamp": wt[Kf - 1]})
     view = None
-    if env.cfg.norm_type in (L.NORM_NONE, L.NORM_LOG):
+    if args.full and env.cfg.norm_type in (L.NORM_NONE, L.NORM_LOG):
         hv = L.HistView()
 
         def run_view(l0, l1):
@@ -1035,6 +1132,8 @@ def windowed(args, world, rank, dev):
             "episodes_completed": int(gathered[:, 3].sum().item()),
             "allgather_path": allgather_path,
         }
+        if dumped:
+            res["dumped_outputs"] = dumped
         if view is not None:
             res["view_mode"] = view
         if wl == "C5":

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${TAG:-ab}; mkdir -p $O
 while IFS='|' read -r name envs args; do
   [ -z "$name" ] && continue
-  env $envs timeout -k 10 300 python -u bench.py $args --no-cpu-baseline > $O/$name.json 2> $O/$name.err \
+  env $envs timeout -k 10 300 python -u bench.py --full $args --no-cpu-baseline > $O/$name.json 2> $O/$name.err \
     || { echo "$name failed"; tail -20 $O/$name.err; exit 1; }
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys

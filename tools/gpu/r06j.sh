@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r06j; mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest_gpu.txt 2>&1 || { echo PYTEST_FAIL; tail -40 $O/pytest_gpu.txt; exit 1; }
 tail -1 $O/pytest_gpu.txt
-timeout -k 10 600 python -u bench.py > $O/bench_driver.json 2> $O/bench_driver.err || { echo DRIVER_FAIL; tail -20 $O/bench_driver.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench_driver.json 2> $O/bench_driver.err || { echo DRIVER_FAIL; tail -20 $O/bench_driver.err; exit 1; }
 python tools/bench_brief.py $O/bench_driver.json 2>/dev/null || tail -c 600 $O/bench_driver.json
 export PLAN="n20_exact||--nstep 20 --nstep-pop exact --steps 20 --warmup 5 --fuse 20 --no-k-sweep --no-cpu-baseline
 n20_running||--nstep 20 --nstep-pop running --steps 20 --warmup 5 --fuse 20 --no-k-sweep

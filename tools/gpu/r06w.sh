@@ -7,5 +7,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -1 $O/pytest_gpu.txt
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { echo SMOKE_FAIL; tail -20 $O/smoke.txt; exit 1; }
 tail -1 $O/smoke.txt
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { echo BENCH_FAIL; tail -20 $O/bench_driver.err; exit 1; }
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { echo BENCH_FAIL; tail -20 $O/bench_driver.err; exit 1; }
 python tools/bench_brief.py $O/bench_driver.json

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 O=gpurun_out/hbm
 mkdir -p $O
 for N in ${N_LIST:-262144 524288}; do
-  B="python bench.py --n-envs $N --steps 512 --warmup 64 --fuse 64 --no-cpu-baseline --no-probe"
+  B="python bench.py --full --n-envs $N --steps 512 --warmup 64 --fuse 64 --no-cpu-baseline --no-probe"
   timeout -k 10 300 $B > $O/bench_$N.json 2> $O/bench_$N.err || { echo "bench $N failed"; tail -20 $O/bench_$N.err; exit 1; }
   cat $O/bench_$N.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$N -o kt -- $B > $O/kt_$N.log 2>&1 || { echo "kt $N failed"; tail -20 $O/kt_$N.log; exit 1; }

@@ -20,10 +20,10 @@ if [ -n "$SUITE" ]; then
 fi
 line() {  # name, args...
   local n=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $O/$n.json 2> $O/$n.err || { echo "$n failed"; tail -20 $O/$n.err; exit 1; }
+  timeout -k 10 400 python bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { echo "$n failed"; tail -20 $O/$n.err; exit 1; }
   python tools/bench_brief.py $O/$n.json
   if [ -n "$TRACE" ]; then
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o kt -- python3 bench.py "$@" \
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o kt -- python3 bench.py --full "$@" \
       > $O/kt_$n.json 2> $O/kt_$n.log || { echo "$n trace failed"; tail -20 $O/kt_$n.log; exit 1; }
     python tools/kt_brief.py $O/kt_$n
     python tools/bench_brief.py $O/kt_$n.json

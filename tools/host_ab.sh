@@ -14,7 +14,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
     n=${v%%|*}; a=${v#*|}
     envs=""; args=""
     for w in $a; do case $w in *=*) envs="$envs $w";; *) args="$args $w";; esac; done
-    env $envs timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-probe --no-k-sweep $args \
+    env $envs timeout -k 10 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-probe --no-k-sweep $args \
       > $O/${n}_$r.json 2> $O/${n}_$r.err || { echo "$n $r failed"; tail -5 $O/${n}_$r.err; exit 1; }
     python -c "import json;d=json.loads(open('$O/${n}_$r.json').read().strip().splitlines()[-1]);print('$n $r region_us %.2f kernel_us %.2f' % (d['ms_per_step']*1e3*d['steps'], d['roofline']['avg_launch_us']))"
   done
