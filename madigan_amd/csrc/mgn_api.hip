@@ -67,8 +67,8 @@ struct mgn_env {
   int m = 1;  // assets per lane
   int sched = MGN_SCHED_AUTO;  // requested step schedule
   bool layout_auto = true;     // assets per lane chosen by auto_layout
-  bool duo = false;            // the two-role kernel runs the steps
-  bool trio = false;           // the three-role pipelined kernel runs the steps
+  mgn::Family family = mgn::Family::Single;  // the kernel family that runs the steps (mgn_select.h)
+  bool nst_run = false;        // MGN_NSTEP_POP_RUNNING granted (nst_run_granted)
   // launch history (mgn_rollout_hist): grown on demand, owned by the handle;
   // two buffers when the gathers run on a window stream (one is written by
   // the next step launch while the other is gathered)
@@ -176,6 +176,11 @@ int fail(mgn_env* e, int code, const std::string& msg) {
 int check_hip(mgn_env* e, hipError_t st, const char* what) {
   if (st == hipSuccess) return MGN_OK;
   return fail(e, MGN_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(st));
+}
+
+// the status of a step launch: launch_step's own error, else HIP's last
+int check_step(mgn_env* e, hipError_t st, const char* what) {
+  return check_hip(e, st != hipSuccess ? st : hipGetLastError(), what);
 }
 
 int validate(const mgn_config* c, const mgn_asset_source* s, std::string& msg) {
@@ -311,7 +316,7 @@ mgn::KParams kparams(const mgn_env* e) {
   // MGN_NSTEP_POP_RUNNING: the shapers with a running-sum pop, scalar
   // rewards, and a discount whose slides stay well conditioned (the sums'
   // rounding grows by 1/gamma per pop between the re-sums every n pops)
-  p.nst_run = nst_run_granted(e) ? 1 : 0;
+  p.nst_run = e->nst_run ? 1 : 0;
   p.nst_rg = p.nst_run ? 1.0 / c.discount : 0.;
   p.nst_rg2 = (p.nst_run && c.shaper == MGN_SHAPER_SORTINO_B) ? 1.0 / std::pow(c.discount, 1.0 / c.sortino_exp) : 0.;
   p.disc2 = e->disc_dev + c.nstep;
@@ -326,176 +331,73 @@ mgn::KParams kparams(const mgn_env* e) {
   return p;
 }
 
-template <typename Arg>
-void launch(void (*const* fns)(int, const Arg&), int apad, int m, const Arg& a) {
-  const int idx = apad <= 1 ? 0 : apad <= 2 ? 1 : apad <= 4 ? 2 : apad <= 8 ? 3 : apad <= 16 ? 4 : apad <= 32 ? 5 : 6;
-  fns[idx](m, a);
+// what the step-kernel selection (mgn_select.h) reads of a handle; the launch
+// fields (gkind, om, in_kind, K) as given
+mgn::StepKey step_key(const mgn_env* e, int gkind = -1, uint32_t om = 0, int in_kind = mgn::IN_DISCRETE,
+                      int K = 1) {
+  mgn::StepKey k{};
+  k.N = e->N; k.A = e->A; k.apad = e->apad; k.W = e->W; k.D = e->D; k.F = e->F;
+  k.nstep = e->cfg.nstep; k.m = e->m;
+  k.replay = e->replay; k.aux = e->cfg.aux != 0;
+  k.gkind = gkind; k.om = om;
+  k.reqm_one = e->cfg.required_margin == 1.0;
+  k.shaper = e->cfg.shaper;
+  k.nst_run = e->nst_run;
+  k.sched = e->sched;
+  k.in_kind = in_kind; k.K = K;
+  k.ablate = e->ablate != 0;
+  return k;
 }
-void (*const kStep[7])(int, const mgn::StepArgs&) = {mgn::launch_step_a1, mgn::launch_step_a2, mgn::launch_step_a4, mgn::launch_step_a8, mgn::launch_step_a16, mgn::launch_step_a32, mgn::launch_step_a64};
-void (*const kDuo[7])(const mgn::StepArgs&) = {mgn::launch_duo_a1, mgn::launch_duo_a2, mgn::launch_duo_a4, mgn::launch_duo_a8, mgn::launch_duo_a16, mgn::launch_duo_a32, mgn::launch_duo_a64};
-void (*const kTrio[7])(const mgn::StepArgs&) = {mgn::launch_trio_a1, mgn::launch_trio_a2, mgn::launch_trio_a4, mgn::launch_trio_a8, mgn::launch_trio_a16, mgn::launch_trio_a32, mgn::launch_trio_a64};
+
+// what follows from a handle's configuration (at creation, and when
+// mgn_set_layout, mgn_set_schedule or mgn_load_state change it): the
+// running-sum pop's grant, the assets per lane (automatic unless
+// mgn_set_layout fixed them) and the schedule
+void auto_layout(mgn_env* e) {
+  e->nst_run = nst_run_granted(e);
+  if (e->layout_auto) e->m = mgn::auto_m(step_key(e));
+  e->family = mgn::choose_sched(step_key(e));
+}
+
+// every unit's step entry, by mgn::Unit
+using StepFn = bool (*)(const mgn::StepChoice&, const mgn::StepArgs&);
+#define MGN_X(u) mgn::launch_##u,
+constexpr StepFn kUnit[] = {MGN_UNITS(MGN_X)};
+#undef MGN_X
+static_assert(sizeof(kUnit) / sizeof(kUnit[0]) == mgn::U_COUNT, "MGN_UNITS lists every unit of enum Unit");
+
+template <typename Arg>
+void launch(void (*const* fns)(int, const Arg&), const mgn_env* e, const Arg& a) {
+  fns[mgn::apad_unit(e->apad)](mgn::single_m(e->apad, e->m), a);
+}
 void (*const kInit[7])(int, const mgn::InitArgs&) = {mgn::launch_init_a1, mgn::launch_init_a2, mgn::launch_init_a4, mgn::launch_init_a8, mgn::launch_init_a16, mgn::launch_init_a32, mgn::launch_init_a64};
 void (*const kVal[7])(int, const mgn::ValArgs&) = {mgn::launch_val_a1, mgn::launch_val_a2, mgn::launch_val_a4, mgn::launch_val_a8, mgn::launch_val_a16, mgn::launch_val_a32, mgn::launch_val_a64};
 
-void launch_step(const mgn_env* e, const mgn_traj& out, int in_kind, const double* units,
-                 const int32_t* aidx, const int8_t* act, int K, hipEvent_t ev0 = nullptr,
-                 hipEvent_t ev1 = nullptr);
-void launch_init(const mgn_env* e, int mode, const uint8_t* mask);
-void launch_val(const mgn_env* e, double* out);
-
-// Lane layout: as few lanes per env as keeps >= 2 waves per SIMD resident
-// (256 CUs x 4 SIMDs x 2), so large batches run thread-per-env-like (less
-// cross-lane work per env) and small batches spread each env over more lanes.
-// the two-role kernel: one lane per asset per role, padded width 2..16,
-// generator sources or a replay tape; n-step buffers (generator sources)
-// while the envs' rings fit the LDS budget (k_step handles the rest and the
-// multi-component sources)
-constexpr size_t kDuoNstLds = 64 * 1024;
-bool duo_eligible(const mgn_env* e) {
-  if (e->apad < 2 || e->apad > 16 || e->cfg.aux) return false;
-  if (e->cfg.nstep > 1) {
-    const size_t epb = (size_t)(256 / e->apad);  // DUO_BLOCK / 2 lanes per role (mgn_duo.h)
-    if (e->replay || epb * e->cfg.nstep * (e->D + 1) * sizeof(double) > kDuoNstLds) return false;
-  }
-  return true;
-}
-// the three-role kernel: 1..16 assets (one asset on two lanes per role, the
-// second a pad), generator sources (replay tapes at 16 assets on the 256-lane
-// layout); one-step rewards or n-step aggregation of a scalar reward (the
-// finish role's rings in dynamic LDS), with or without a window (the
-// confirmed steps' rows are pushed by its finish role).  Some launches of an
-// eligible handle have no instantiation (trio_launchable) and run another
-// kernel -- every kernel reads and writes the same state, bit-identically
-bool trio_eligible(const mgn_env* e) {
-  // (its output indices are k x a 32-bit stride: N (A + 1), N F and N n fit 32 bits)
-  const uint64_t row = (uint64_t)(e->A + 1 > e->F ? e->A + 1 : e->F);
-  const bool nst_ok = e->cfg.nstep == 1 || e->D == 1;
-  // replay tapes: 16 assets at the 256-lane layout (N * 16 >= 256 * 256), n = 1
-  const bool rp_ok = !e->replay || (e->apad == 16 && e->cfg.nstep == 1 && (uint64_t)e->N * 16 >= 65536);
-  if (!(e->apad >= 1 && e->apad <= 16 && !e->cfg.aux && rp_ok && nst_ok &&
-        (uint64_t)e->N * row < (1ull << 32) && (uint64_t)e->N * (uint64_t)e->cfg.nstep < (1ull << 32)))
-    return false;
-  // n-step: the static arrays plus the envs' rings in dynamic LDS within a
-  // workgroup's 160 KiB (2 assets at n = 64 would need more: the two-role /
-  // single-role kernels run those)
-  if (e->cfg.nstep > 1) {
-    // (one asset: the two-lane layout's, APAD 2)
-    static size_t (*const lds_of[5])(long long, int, bool) = {nullptr, mgn::trio_nst_lds_a2, mgn::trio_nst_lds_a4,
-                                                              mgn::trio_nst_lds_a8, mgn::trio_nst_lds_a16};
-    const int idx = e->apad <= 2 ? 1 : e->apad <= 4 ? 2 : e->apad <= 8 ? 3 : 4;
-    if (lds_of[idx](e->N, e->cfg.nstep, e->W > 0) > mgn::kTrioLdsMax) return false;
-  }
-  return true;
-}
-// the launches of a three-role handle with an instantiation: discrete steps
-// (the agent loop) always; units / single orders unless the env has one asset
-// or keeps a window with n-step rings
-bool trio_launchable(const mgn_env* e, int in_kind) {
-  if (in_kind == mgn::IN_DISCRETE) return true;
-  return e->apad > 1 && !(e->W > 0 && e->cfg.nstep > 1);
-}
-// automatic: where the single-role kernel would run one lane per asset (small
-// batches: one wave per SIMD), give every asset a second (and a third) lane
-// in partner waves
-void choose_sched(mgn_env* e) {
-  e->trio = false;
-  if (e->sched == MGN_SCHED_SINGLE) {
-    e->duo = false;
-  } else if (e->sched == MGN_SCHED_DUO) {
-    e->duo = duo_eligible(e);
-  } else if (e->sched == MGN_SCHED_TRIO) {
-    e->trio = trio_eligible(e);
-    e->duo = !e->trio && duo_eligible(e);
-  } else {
-    // 16 assets: the three-role kernel where measured faster -- generator
-    // sources with one-step rewards and no window (5.2 vs 6.3 us/step at
-    // 8192 x 16 TrendOU) and replay tapes (C5: 405 vs 485 us per 64-step launch),
-    // and, where its two-slots-per-lane layout runs the agent loop's discrete
-    // steps (trio_m2_ok), windowed generator handles too
-    // one asset with a window: the two-lane layout's one-wave-per-role grid
-    // holds 16384 envs in one round (two workgroups per CU); beyond it the
-    // single-role kernel's one lane per env measured faster (R1 at 65536:
-    // 1098 vs 1507 us per 64-step launch, profiles/r05c_bench_R1_64k{_single,}.json;
-    // at 8192 envs the three-role kernel 337 vs 809, r05c_bench_R1_8k{,_single}.json)
-    // -- with the exact n-step pop.  With the running-sum pop (which only the
-    // three-role kernel has) it stays faster at every batch: R1 at 65536 695
-    // vs 1141 us, at 32768 398 vs 896 (profiles/r06p_*.json)
-    const bool one_win_big = e->apad == 1 && e->W > 0 && e->N > 16384 && !nst_run_granted(e);
-    e->trio = trio_eligible(e) && e->m == 1 && !one_win_big &&
-              (e->apad <= 8 ||
-               (e->apad <= 16 && ((e->W == 0 && e->cfg.nstep == 1) || e->replay ||
-                                  mgn::trio_m2_ok(e->N, e->A, e->cfg.nstep, e->D, mgn::IN_DISCRETE))));
-    e->duo = !e->trio && duo_eligible(e) && e->m == 1;
-  }
-}
-int choose_m(int n_envs, int apad);
-// automatic layout: the two-role kernel wherever it is eligible (at C3 it runs
-// 2.8e9 env-steps/s at 8192 envs and 3.0e9 at 65536, where the single-role
-// layout rule below would pick 4 assets per lane and run 1.7e9); else as few
-// lanes per env as keep >= 2 waves per SIMD
-void auto_layout(mgn_env* e) {
-  if (e->layout_auto)
-    e->m = (e->sched != MGN_SCHED_SINGLE && (duo_eligible(e) || trio_eligible(e))) ? 1 : choose_m(e->N, e->apad);
-  choose_sched(e);
-}
-
-int choose_m(int n_envs, int apad) {
-  int m = mgn::min_m(apad);
-  while (m < 8 && m < apad) {
-    const long long waves = (long long)n_envs * (apad / (2 * m)) / 64;
-    if (waves < 2048) break;
-    m *= 2;
-  }
-  return m;
-}
-
-void launch_step(const mgn_env* e, const mgn_traj& out, int in_kind, const double* units,
-                 const int32_t* aidx, const int8_t* act, int K, hipEvent_t ev0, hipEvent_t ev1) {
-  mgn::StepArgs a{kparams(e), out, in_kind, units, aidx, act, K, e->stream, ev0, ev1};
+// launches the step kernel mgn_select.h chooses.  A choice no unit serves, or
+// a dynamic LDS size the device refuses, is an error (the caller's check_hip
+// reports it), never a step that silently did nothing
+hipError_t launch_step(const mgn_env* e, const mgn_traj& out, int in_kind, const double* units,
+                       const int32_t* aidx, const int8_t* act, int K, hipEvent_t ev0 = nullptr,
+                       hipEvent_t ev1 = nullptr) {
+  const mgn::StepArgs a{kparams(e), out, in_kind, units, aidx, act, K, e->stream, ev0, ev1};
+  int gkind = -1;
 #if !(defined(MGN_DIAG) && defined(MGN_NO_GK))  // diagnostic A/B builds: the generic generator role everywhere
-  a.gkind = e->kinds[0];
+  gkind = e->kinds[0];
   for (int i = 1; i < e->A; ++i)
-    if (e->kinds[i] != a.gkind) a.gkind = -1;
+    if (e->kinds[i] != gkind) gkind = -1;
 #endif
-  // a 9..16-asset window handle takes the three-role kernel (automatic
-  // schedule) for the launches its two-slot layout runs -- discrete steps,
-  // trio_m2_ok; its one-slot layout measured slower than the two-role kernel
-  // there, so the handle's other launches (units, single orders) run that
-  bool trio = e->trio;
-  if (trio && e->sched == MGN_SCHED_AUTO && e->apad > 8 && e->W > 0 && !e->replay &&
-      !mgn::trio_m2_ok(e->N, e->A, e->cfg.nstep, e->D, in_kind) && duo_eligible(e)) {
-    kDuo[4](a);
-    return;
-  }
-  if (trio && !trio_launchable(e, in_kind)) {
-    // no three-role instantiation for this launch: the two-role kernel where
-    // eligible, else the single-role one (same state, same bits)
-    if (duo_eligible(e)) {
-      kDuo[e->apad <= 2 ? 1 : e->apad <= 4 ? 2 : e->apad <= 8 ? 3 : 4](a);
-      return;
-    }
-    launch(kStep, e->apad, e->m, a);
-    return;
-  }
-  if (trio) {
-    const int idx = e->apad <= 2 ? 1 : e->apad <= 4 ? 2 : e->apad <= 8 ? 3 : 4;
-    kTrio[idx](a);
-    return;
-  }
-  if (e->duo) {
-    const int idx = e->apad <= 2 ? 1 : e->apad <= 4 ? 2 : e->apad <= 8 ? 3 : 4;
-    kDuo[idx](a);
-    return;
-  }
-  launch(kStep, e->apad, e->m, a);
+  const mgn::StepChoice c = mgn::select_step(step_key(e, gkind, mgn::traj_mask(out), in_kind, K));
+  if (c.unit != mgn::U_NONE && kUnit[c.unit](c, a)) return hipSuccess;
+  const hipError_t st = hipGetLastError();
+  return st != hipSuccess ? st : hipErrorInvalidDeviceFunction;
 }
 void launch_init(const mgn_env* e, int mode, const uint8_t* mask) {
   mgn::InitArgs a{kparams(e), mode, mask, e->stream};
-  launch(kInit, e->apad, e->m, a);
+  launch(kInit, e, a);
 }
 void launch_val(const mgn_env* e, double* out) {
   mgn::ValArgs a{kparams(e), out, e->stream};
-  launch(kVal, e->apad, e->m, a);
+  launch(kVal, e, a);
 }
 
 mgn::RingDesc ring_desc(const mgn_env* e) {
@@ -727,8 +629,8 @@ int mgn_step(mgn_env* e, int32_t kind, const double* units_dev, const int32_t* a
   if (in_kind != mgn::IN_NONE && !units_dev) return fail(e, MGN_ERR_ARG, "units pointer is null");
   if (in_kind == mgn::IN_SINGLE && !aidx_dev) return fail(e, MGN_ERR_ARG, "asset index pointer is null");
   if (need_tape(e) != MGN_OK) return MGN_ERR_CONFIG;
-  launch_step(e, e->v.out, in_kind, units_dev, aidx_dev, nullptr, 1);
-  return check_hip(e, hipGetLastError(), "mgn_step");
+  const hipError_t lst = launch_step(e, e->v.out, in_kind, units_dev, aidx_dev, nullptr, 1);
+  return check_step(e, lst, "mgn_step");
 }
 
 static void time_mark(mgn_env* e, std::vector<hipEvent_t>& v, size_t& n, hipStream_t st);
@@ -742,9 +644,9 @@ int mgn_rollout(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, const mg
   hipEvent_t a = nullptr, b = nullptr;
   if (e->timing == 2) (void)time_pair(e, a, b);
   else time_mark(e, e->t_step, e->t_step_n, e->stream);
-  launch_step(e, *out, mgn::IN_DISCRETE, nullptr, nullptr, actions_dev, (int)k_steps, a, b);
+  const hipError_t lst = launch_step(e, *out, mgn::IN_DISCRETE, nullptr, nullptr, actions_dev, (int)k_steps, a, b);
   if (e->timing != 2) time_mark(e, e->t_step, e->t_step_n, e->stream);
-  return check_hip(e, hipGetLastError(), "mgn_rollout");
+  return check_step(e, lst, "mgn_rollout");
 }
 
 int mgn_rollout_units(mgn_env* e, const double* units_dev, int32_t k_steps, const mgn_traj* out) {
@@ -752,8 +654,8 @@ int mgn_rollout_units(mgn_env* e, const double* units_dev, int32_t k_steps, cons
   if (!units_dev || !out) return fail(e, MGN_ERR_ARG, "null units/out");
   if (k_steps < 1) return fail(e, MGN_ERR_LENGTH, "k_steps must be >= 1");
   if (need_tape(e) != MGN_OK) return MGN_ERR_CONFIG;
-  launch_step(e, *out, mgn::IN_UNITS, units_dev, nullptr, nullptr, (int)k_steps);
-  return check_hip(e, hipGetLastError(), "mgn_rollout_units");
+  const hipError_t lst = launch_step(e, *out, mgn::IN_UNITS, units_dev, nullptr, nullptr, (int)k_steps);
+  return check_step(e, lst, "mgn_rollout_units");
 }
 
 int mgn_set_prices(mgn_env* e, const double* prices_dev) {
@@ -933,12 +835,12 @@ int mgn_rollout_hist(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, con
                      hb.ts, (int)rows);
   time_mark(e, e->t_step, e->t_step_n, e->stream);
   e->hist_on = true;
-  launch_step(e, *out, mgn::IN_DISCRETE, nullptr, nullptr, actions_dev, (int)k_steps);
+  const hipError_t lst = launch_step(e, *out, mgn::IN_DISCRETE, nullptr, nullptr, actions_dev, (int)k_steps);
   e->hist_on = false;
   time_mark(e, e->t_step, e->t_step_n, e->stream);
   hb.k = k_steps;
   if (e->wstream) (void)hipEventRecord(hb.ready, e->stream);
-  return check_hip(e, hipGetLastError(), "mgn_rollout_hist");
+  return check_step(e, lst, "mgn_rollout_hist");
 }
 
 int mgn_window_hist(mgn_env* e, double* price_dev, double* port_dev, uint64_t* ts_dev) {
@@ -1143,7 +1045,7 @@ int mgn_set_layout(mgn_env* e, int32_t assets_per_lane) {
   if (m < mgn::min_m(e->apad)) m = mgn::min_m(e->apad);
   e->m = m;
   e->layout_auto = false;
-  choose_sched(e);
+  auto_layout(e);
   return MGN_OK;
 }
 
@@ -1151,10 +1053,10 @@ int mgn_set_schedule(mgn_env* e, int32_t schedule) {
   if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
   if (schedule < MGN_SCHED_AUTO || schedule > MGN_SCHED_TRIO)
     return fail(e, MGN_ERR_CONFIG, "schedule must be MGN_SCHED_AUTO, _SINGLE, _DUO or _TRIO");
-  if (schedule == MGN_SCHED_DUO && !duo_eligible(e))
+  if (schedule == MGN_SCHED_DUO && !mgn::duo_eligible(step_key(e)))
     return fail(e, MGN_ERR_CONFIG,
                 "the two-role kernel needs 2..16 assets, no multi-component source, n-step rings within LDS");
-  if (schedule == MGN_SCHED_TRIO && !trio_eligible(e))
+  if (schedule == MGN_SCHED_TRIO && !mgn::trio_eligible(step_key(e)))
     return fail(e, MGN_ERR_CONFIG,
                 "the three-role kernel needs 2..16 assets, generator sources (or a replay tape at 16 assets), nstep 1 or a scalar n-step reward without a window whose rings fit LDS");
   e->sched = schedule;
@@ -1163,7 +1065,8 @@ int mgn_set_schedule(mgn_env* e, int32_t schedule) {
 }
 
 int mgn_get_schedule(const mgn_env* e) {
-  return e ? (e->trio ? MGN_SCHED_TRIO : e->duo ? MGN_SCHED_DUO : MGN_SCHED_SINGLE) : 0;
+  if (!e) return 0;
+  return e->family == mgn::Family::Trio ? MGN_SCHED_TRIO : e->family == mgn::Family::Duo ? MGN_SCHED_DUO : MGN_SCHED_SINGLE;
 }
 
 int mgn_get_layout(const mgn_env* e) { return e ? e->m : 0; }

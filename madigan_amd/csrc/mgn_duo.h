@@ -35,10 +35,6 @@
 
 namespace mgn {
 
-constexpr int DUO_BLOCK = 512;
-
-constexpr int DUO_HALF = DUO_BLOCK / 2;
-
 enum { REC_STEP = 1, REC_TICK = 2, REC_DONE = 4, REC_MCALL = 8 };
 
 // step record of lane / env (ledger -> generator waves)
@@ -76,9 +72,7 @@ struct DuoShared {
 // instructions, and FLAT counts on lgkmcnt as well as vmcnt -- every LDS
 // wait and every barrier of the step loop then waited for the previous
 // stores (and the next action's load) to complete in memory.
-enum : uint32_t { O_REW = 1u, O_AREW = 2u, O_SHP = 4u, O_DONE = 8u, O_OPR = 16u, O_OPT = 32u,
-                  O_TS = 64u, O_TP = 128u, O_TU = 256u, O_TC = 512u, O_RISK = 1024u,
-                  O_MC = 2048u, O_NSH = 4096u, O_DEND = 8192u };
+// (the O_* field bits and the output sets O_STD / O_ALL / O_STDN / O_WSTD: mgn_consts.h)
 __host__ __device__ __forceinline__ uint32_t traj_mask(const mgn_traj& o) {
   return (o.reward ? O_REW : 0u) | (o.agent_reward ? O_AREW : 0u) | (o.shaped ? O_SHP : 0u) |
          (o.done ? O_DONE : 0u) | (o.obs_price ? O_OPR : 0u) | (o.obs_port ? O_OPT : 0u) |
@@ -125,15 +119,6 @@ __device__ __forceinline__ GTraj traj_vgpr(const mgn_traj& o) {
   if (M & O_DEND) v.data_end = vptr(o.data_end);
   return v;
 }
-// the output sets with their own trio instantiations: every field, and the
-// agent loop's State + EnvInfo + reward + shaped reward (no agent reward,
-// n_shaped or data_end)
-constexpr uint32_t O_ALL = 16383u;
-constexpr uint32_t O_STD = O_REW | O_SHP | O_DONE | O_OPR | O_OPT | O_TS | O_TP | O_TU | O_TC | O_RISK | O_MC;
-// an n-step agent loop's: O_STD and the popped-value counts
-constexpr uint32_t O_STDN = O_STD | O_NSH;
-// a windowed n-step agent loop's (bench.py windowed()): O_STDN and data_end
-constexpr uint32_t O_WSTD = O_STD | O_DEND | O_NSH;
 // element index k * stride + base as one 32 x 32 + 64 multiply-add (the
 // host checks that every stride fits 32 bits)
 __device__ __forceinline__ size_t kidx(int k, uint32_t stride, size_t base) {
@@ -846,7 +831,7 @@ __device__ __forceinline__ void duo_replay_tick(Lane<1>& s, const KParams& p, ui
 // every asset from the replay tape (mgn_attach_replay): the generator lanes
 // read the tape, one row ahead, instead of ticking a generator.  NST: n-step
 // aggregation (nstep > 1) on the generator side, each env's (n, D) ring and
-// an n-entry pop scratch in dynamic LDS (launch_duo sizes it: envs per block
+// an n-entry pop scratch in dynamic LDS (duo_nst_lds, mgn_select.h: envs per block
 // x n x (D + 1) doubles).
 // the exit test after barrier B of iteration j: the ledger runs at most one
 // step per iteration, so every iteration j < K - 1 is followed by another and

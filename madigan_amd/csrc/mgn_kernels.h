@@ -19,12 +19,11 @@
 #include <stdint.h>
 
 #include "../../include/madigan_amd.h"
+#include "mgn_consts.h"
 #include "mgn_diag.h"
 #include "mgn_math.h"
 
 namespace mgn {
-
-constexpr int BLOCK = 256;
 
 // wait for every outstanding vector-memory load / store of this wave, as a
 // real S_WAITCNT (gfx9 simm16: vmcnt 0, expcnt 7, lgkmcnt 15) that the
@@ -1107,9 +1106,6 @@ __device__ __forceinline__ void broker_x(Lane<M>& s, const KParams& p, EnvRecs<M
   after.sh = t[2][1];
   after.b = t[3][1];
 }
-
-// input selector
-enum { IN_NONE = 0, IN_UNITS = 1, IN_SINGLE = 2, IN_DISCRETE = 3 };
 
 __device__ __forceinline__ double dsr_one(double r, double A, double B) {
   const double dA = r - A;

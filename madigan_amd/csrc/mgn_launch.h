@@ -1,6 +1,9 @@
-// mgn_launch.h -- host-side launchers of the templated step kernels.  Each
-// padded asset count APAD has its own translation unit (mgn_launch_a<APAD>.hip)
-// so the (M, S) instantiations compile in parallel.
+// mgn_launch.h -- host-side launchers of the templated step kernels.  The
+// kernels are instantiated in 17 translation units (mgn_launch_<unit>.hip:
+// one per padded asset count, and units of their own for instantiations built
+// with other flags) that compile in parallel.  Which kernel runs a launch is
+// decided in mgn_select.h; a unit only maps the choice onto the kernels it
+// instantiates (mgn_units.h) and launches it.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -8,6 +11,7 @@
 
 #include "mgn_duo.h"
 #include "mgn_kernels.h"
+#include "mgn_units.h"
 
 namespace mgn {
 
@@ -24,9 +28,6 @@ struct StepArgs {
   // itself (hipExtLaunchKernel: the kernel's own begin / end, no marker
   // packets around it); null otherwise
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // the source kind shared by every asset of the handle, else -1 (selects the
-  // kind-specialized generator role where one is instantiated)
-  int gkind = -1;
 };
 // hipLaunchKernelGGL, or the event-recording launch when the step's events are set
 template <typename Kern, typename... Args>
@@ -47,46 +48,16 @@ struct ValArgs {
   hipStream_t stream;
 };
 
-// a workgroup's LDS on gfx950 (the three-role kernel's n-step eligibility)
-constexpr size_t kTrioLdsMax = 160 * 1024;
+// every unit's one step entry: launches the chosen kernel; false when the unit
+// instantiates none that matches or the device refuses its dynamic LDS size
+#define MGN_X(u) bool launch_##u(const StepChoice& c, const StepArgs& a);
+MGN_UNITS(MGN_X)
+#undef MGN_X
 
-// the three-role kernel's two-slots-per-lane layout (launch_trio_m2): 9..16
-// assets at the 256-lane layout (N x 16 >= 256 x 256 lanes), discrete
-// actions, one-step rewards with a scalar shaper
-inline bool trio_m2_ok(long long n_envs, int A, int nstep, int D, int in_kind) {
-  return A > 8 && A <= 16 && n_envs * 16 >= 65536 && nstep == 1 && D == 1 &&
-         in_kind == IN_DISCRETE;
-}
-void launch_trio_m2_a16(const StepArgs& a);
-// the agent loop's three-role launches at APAD = 8 (the C3 headline), in units
-// of their own: multi-step (mgn_launch_a8t.hip), one-step (mgn_launch_a8k1.hip)
-void launch_trio_agent_a8(const StepArgs& a);
-void launch_trio_agent_k1_a8(const StepArgs& a);
-void launch_trio_agent_k1w_a8(const StepArgs& a);
-// one-step launches at APAD 8 from this many envs on: the wide unit
-// (mgn_launch_a8k1w.hip, four waves per SIMD)
-constexpr int kTrioK1WideN = 65536;
-// the n-step three-role launches, in units of their own
-// (mgn_launch_a{2,4,8,16}nst.hip: built without machine LICM)
-void launch_trio_nst_a2(const StepArgs& a);
-void launch_trio_nst_a4(const StepArgs& a);
-void launch_trio_nst_a8(const StepArgs& a);
-void launch_trio_nst_a16(const StepArgs& a);
-// the three-role kernel for one-asset envs (ONE: S = 2 lanes, the second a
-// pad), in its own unit (mgn_launch_a1t.hip; the n-step handles in
-// mgn_launch_a1tnst.hip): discrete steps (the agent loop)
-void launch_trio_one(const StepArgs& a);
-void launch_trio_one_nst(const StepArgs& a);
-
-// smallest assets-per-lane with at most 16 lanes per env (DPP-only reductions)
-constexpr int min_m(int apad) { return apad > 16 ? apad / 16 : 1; }
-
-#define MGN_DECLARE_APAD(A)                          \
-  void launch_duo_a##A(const StepArgs& a);           \
-  void launch_trio_a##A(const StepArgs& a);          \
-  size_t trio_nst_lds_a##A(long long n_envs, int nstep, bool win); \
-  void launch_step_a##A(int m, const StepArgs& a);   \
-  void launch_init_a##A(int m, const InitArgs& a);   \
+// Env construction / reset and valuation: the single-role layout's kernels,
+// m = single_m(APAD, assets per lane)
+#define MGN_DECLARE_APAD(A)                        \
+  void launch_init_a##A(int m, const InitArgs& a); \
   void launch_val_a##A(int m, const ValArgs& a);
 MGN_DECLARE_APAD(1)
 MGN_DECLARE_APAD(2)

@@ -1,10 +1,8 @@
 // the three-role kernel's two-slots-per-lane layout for 9..16 assets
-// (launch_trio_m2, mgn_launch_impl.h): its own unit for its own flags
+// (trio_m2_list, mgn_units.h): its own unit for its own flags
 // (madigan_amd/build.py UNIT_FLAGS)
 #include "mgn_launch_impl.h"
-namespace mgn {
-void launch_trio_m2_a16(const StepArgs& a) { launch_trio_m2<8>(a); }
-}  // namespace mgn
+MGN_DEFINE_UNIT(a16m2)
 #if defined(MGN_STAMPS)
 // diagnostic build: this unit's own copy of the per-role stamps (the
 // two-slot kernels run here; mgn_diag_stamps reads the A = 8 unit's)

@@ -1,7 +1,5 @@
-// the three-role kernel's n-step instantiations at APAD = 4 (launch_trio_nst,
-// mgn_launch_impl.h): their own unit for their own flags
+// the three-role kernel's n-step instantiations at APAD = 4 (trio_nst_list,
+// mgn_units.h): their own unit for their own flags
 // (madigan_amd/build.py UNIT_FLAGS)
 #include "mgn_launch_impl.h"
-namespace mgn {
-void launch_trio_nst_a4(const StepArgs& a) { launch_trio_nst<4>(a); }
-}  // namespace mgn
+MGN_DEFINE_UNIT(a4nst)

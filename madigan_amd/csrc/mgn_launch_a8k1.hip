@@ -1,10 +1,8 @@
 // the three-role kernel's one-step agent-loop instantiations at APAD = 8 --
-// the C3 agent loop's K = 1 (launch_trio_agent_k, mgn_launch_impl.h): their
+// the C3 agent loop's K = 1 (trio_agent8_list, mgn_units.h): their
 // own unit, built without machine LICM (madigan_amd/build.py)
 #include "mgn_launch_impl.h"
-namespace mgn {
-void launch_trio_agent_k1_a8(const StepArgs& a) { launch_trio_agent_k<8, true>(a); }
-}  // namespace mgn
+MGN_DEFINE_UNIT(a8k1)
 #ifdef MGN_ITERSTAMP
 // diagnostic build: this unit's copy of the iteration stamps (the one-step
 // launches run here; mgn_diag_iter reads mgn_launch_a8t.hip's)

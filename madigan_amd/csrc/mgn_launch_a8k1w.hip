@@ -1,5 +1,5 @@
 // the one-step agent-loop launches of large batches at APAD = 8 (N >= 65536
-// envs, launch_trio_agent): one wave per role (192-thread workgroups) at four
+// envs, mgn_select.h): one wave per role (192-thread workgroups) at four
 // waves per SIMD (MGN_TRIO_WPE4: 128 VGPRs), so five workgroups share a CU
 // and their serial chains (state loads, orders, the finish) overlap -- where
 // the 768-thread layout holds one workgroup per CU and the grid runs in many
@@ -7,6 +7,4 @@
 // 43.0; at 8192 envs, one round, 7.6 against 6.7: profiles/r06qr_k1_ddr_ab.txt)
 #define MGN_TRIO_WPE4 1
 #include "mgn_launch_impl.h"
-namespace mgn {
-void launch_trio_agent_k1w_a8(const StepArgs& a) { launch_trio_agent_k<8, true, 64>(a); }
-}  // namespace mgn
+MGN_DEFINE_UNIT(a8k1w)

@@ -1,10 +1,8 @@
-// the three-role kernel's n-step instantiations at APAD = 8 (launch_trio_nst,
-// mgn_launch_impl.h): their own unit for their own flags
+// the three-role kernel's n-step instantiations at APAD = 8 (trio_nst_list,
+// mgn_units.h): their own unit for their own flags
 // (madigan_amd/build.py UNIT_FLAGS)
 #include "mgn_launch_impl.h"
-namespace mgn {
-void launch_trio_nst_a8(const StepArgs& a) { launch_trio_nst<8>(a); }
-}  // namespace mgn
+MGN_DEFINE_UNIT(a8nst)
 #if defined(MGN_STAMPS)
 // diagnostic build: this unit's own copy of the per-role stamps (the n-step
 // kernels run here; mgn_diag_stamps reads the A = 8 unit's)

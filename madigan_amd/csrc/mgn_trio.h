@@ -41,14 +41,11 @@
 #pragma once
 
 #include "mgn_duo.h"
+#include "mgn_select.h"
 
 namespace mgn {
 
-constexpr int TRIO_BLOCK = 768;
-constexpr int TRIO_W = 256;  // lanes per role
-// TW = 64 (one wave per role, 192-thread workgroups): small batches, whose
-// 256-lane workgroups would leave CUs idle (C2: 4096 envs x 4 assets fill 64
-// of 256 CUs at 256 lanes per role, all of them at 64)
+// (TRIO_BLOCK, TRIO_W and the one-wave-per-role layout TW = 64: mgn_consts.h)
 
 // the roles' issue priorities (s_setprio; the ledger's orders are the
 // critical path -- equal priorities measured slower, round 2)
@@ -116,15 +113,6 @@ __device__ __forceinline__ bool rec_done(const double (&Lr)[M], const double (&P
 // window row, nothing else
 enum { TR_STEP = 1, TR_ANYMC = 2, TR_MCALL = 4, TR_REFILL = 8 };
 
-// NST: per env, the ring and the pop's summands in slots of nst_pad(n, S)
-// doubles: n rounded up to a multiple of max(8, S) -- a pop writes whole
-// rounds of S summands (R S slots, R = ceil(len / S)) and the ordered sum
-// reads R S / 2 pairs, so at S = 16 a multiple of 8 would run into the next
-// env's ring; 64-B aligned
-__host__ __device__ constexpr int nst_pad(int n, int S) {
-  return (n + (S > 8 ? S : 8) - 1) / (S > 8 ? S : 8) * (S > 8 ? S : 8);
-}
-
 // per asset slot (M per lane: slot (env, asset) at el APAD + ls M + m)
 template <int S, int TW = TRIO_W, int M = 1>
 struct TrioShared {
@@ -158,14 +146,21 @@ struct TrioShared {
 
 // LDS of k_step_trio<S, ..., TW, NST, ..., M>: its static arrays (an upper
 // bound of the compiler's layout) plus, for NST, the rings in dynamic LDS; the
-// launcher's eligibility test keeps the sum within a workgroup's 160 KiB
-// (kTrioLdsMax, mgn_launch.h)
+// host's eligibility test (trio_eligible, mgn_select.h) keeps the sum within
+// a workgroup's 160 KiB (kTrioLdsMax)
 template <int S, int TW, bool NST, int M = 1>
 constexpr size_t trio_static_lds() {
   return sizeof(TrioShared<S, TW, M>) + (size_t)(TW / S) * sizeof(EnvRecs<S * M>) +
          S * M * sizeof(mgn_asset_source) + (MGN_MAX_ASSETS + 1) * sizeof(double) +
          (NST ? 2 * MGN_MAX_NSTEP : 1) * sizeof(double) + 256;  // s_disc (+ s_disc2 of the running pop)
 }
+// the host-only copy of these sizes the eligibility test reads: a change of
+// the structs fails the build here instead of skewing eligibility
+#define MGN_LDS_IS(S, TW) \
+  static_assert(trio_static_lds<S, TW, true>() == trio_static_lds_nst(S, TW), "update kTrioStaticLds (mgn_select.h)")
+MGN_LDS_IS(2, 64); MGN_LDS_IS(2, TRIO_W); MGN_LDS_IS(4, 64); MGN_LDS_IS(4, TRIO_W);
+MGN_LDS_IS(8, 64); MGN_LDS_IS(8, TRIO_W); MGN_LDS_IS(16, 64); MGN_LDS_IS(16, TRIO_W);
+#undef MGN_LDS_IS
 
 // The replay tape's tick for the lane's M slots (duo_replay_tick's, per slot:
 // feature column fcol + m when the row's features are spread one per slot)
@@ -215,10 +210,6 @@ __device__ __forceinline__ void trio_replay_tick(Lane<M>& s, const KParams& p, u
   nx.dend = p.rp_end[s.rcur];
   s.pf_ok = true;
 }
-// per env: the ring and the finish role's pop summands
-inline size_t trio_nst_dyn_lds(int S, int TW, int nstep) {
-  return (size_t)(TW / S) * 2 * nst_pad(nstep, S) * sizeof(double);
-}
 
 // OMC: the output set when known at compile time (O_ALL, O_STD), else 0.
 // WIN: the handle keeps a window (StackerDiscrete ring, and the launch
@@ -230,7 +221,7 @@ inline size_t trio_nst_dyn_lds(int S, int TW, int nstep) {
 // k_step_duo / k_step.
 // NST: n-step aggregation (nstep > 1, scalar reward D = 1) in the finish
 // role: the env's NStepBuffer ring and one pop's summands in dynamic LDS
-// (launch_trio sizes it: envs per block x 2 nst_pad(n, S) doubles), the discounts staged
+// (trio_nst_dyn_lds: envs per block x 2 nst_pad(n, S) doubles), the discounts staged
 // in LDS, so a pop is n LDS reads issued together, not n dependent loads.
 // GK >= 0: every asset's source is of kind GK (the generator role's per-lane
 // kind dispatch folds away: TrendOU at C3).
