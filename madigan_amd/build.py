@@ -118,6 +118,35 @@ def build_pycall(force: bool = False, verbose: bool = False) -> str:
     return out
 
 
+PROBE_SRC = os.path.join(ROOT, "tests", "csrc", "mgn_math_probe.hip")
+# (not under _obj: the probe is a finished library, used as built wherever the
+# tree is copied; *.so is ignored by git)
+PROBE_OUT = os.path.join(ROOT, "tests", "_probe", "libmgn_math_probe.so")
+PROBE_ENTRIES = ("mgp_abi", "mgp_div_by_rcp", "mgp_rt_div", "mgp_rt_sqrt", "mgp_log_ratio", "mgp_fdlibm", "mgp_block",
+                 "mgp_draw", "mgp_radius", "mgp_shaper", "mgp_canon", "mgp_seg_bcast")
+
+
+def build_math_probe(force: bool = False, verbose: bool = False) -> str:
+    """tests/_probe/libmgn_math_probe.so: the device math helpers of
+    mgn_math.h / mgn_kernels.h behind element-wise kernels, for
+    tests/test_gpu_math_probe.py.  Test infrastructure: compiled with exactly
+    the product's FLAGS, never linked into or loaded by the product library."""
+    deps_ = [PROBE_SRC] + glob.glob(os.path.join(CSRC, "*.h"))
+    if not force and os.path.exists(PROBE_OUT) and all(
+            os.path.getmtime(d) <= os.path.getmtime(PROBE_OUT) for d in deps_):
+        return PROBE_OUT
+    os.makedirs(os.path.dirname(PROBE_OUT), exist_ok=True)
+    cmd = [hipcc(), *FLAGS, f"-I{CSRC}", f"-I{os.path.join(ROOT, 'include')}", "-shared",
+           "-o", PROBE_OUT + ".tmp", PROBE_SRC]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed on {PROBE_SRC}:\n{r.stderr}")
+    os.replace(PROBE_OUT + ".tmp", PROBE_OUT)
+    return PROBE_OUT
+
+
 def deps():
     return sources() + glob.glob(os.path.join(CSRC, "*.h")) + [
         os.path.join(ROOT, "include", "madigan_amd.h")]
@@ -171,6 +200,7 @@ def parse_resource_usage(text: str) -> dict:
 
 def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     build_hdf(force=force, verbose=verbose)
+    build_math_probe(force=force, verbose=verbose)
     if not force and not needs_build():
         _optional_pycall(False, verbose)
         return OUT

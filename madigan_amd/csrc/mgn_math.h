@@ -112,7 +112,17 @@ __device__ __forceinline__ double k_cos(double x, double y) {
 // sin(x) with fdlibm's medium Cody-Waite reduction; det_sin is its called
 // form (the multi-slot kernels), det_sin_inl the inlined one (the pipelined
 // kernels' generator role: a call there spilled live registers to scratch
-// around every Sine tick)
+// around every Sine tick).  Domain: the medium reduction is fdlibm's for
+// |x| <= 2^20 pi/2 ~ 1.647e6, and there the result is within 1 ulp (0.74
+// measured, 0.50 next to multiples of pi/2 where the second and third terms
+// run).  Past it fn * pio2_1 is no longer exact and the absolute error jumps
+// from 8e-17 to 6.5e-10, then grows with |x|: 7.5e-9 to 1e8, 6e-8 to 1e9
+// (the project's bar is 1e-6), 6e-5 to 1e12; from 2^62 on (int64_t)fn is
+// undefined.  Device and oracle stay bit-identical throughout (the same
+// statements; tested to 2^52).  A Sine source's argument is 2 pi freq x with
+// x += dX per tick and no wrap: at the reference's parameters (freq <= 4.7,
+// dX = 0.01) it grows by 0.295 a tick and leaves the domain after 5.6e6
+// ticks, the 1e-6 bar after 3.4e9.
 __device__ __forceinline__ double det_sin_inl(double x) {
   const double invpio2 = bits_to_d(0x3FE45F306DC9C883ull);
   const double pio2_1 = bits_to_d(0x3FF921FB54400000ull), pio2_1t = bits_to_d(0x3DD0B4611A626331ull);
@@ -159,9 +169,17 @@ constexpr double TWO_M32 = 2.3283064365386962890625e-10;
 // feed the ledger, the prices, done or State.  a / b as a times the
 // reciprocal of b refined by two Newton steps (<= 2 ulp; 6 VALU instead of
 // the IEEE sequence's 11), sqrt x from v_rsq_f64 with one Goldschmidt
-// refinement (<= 1 ulp; 8 VALU instead of 17).  Operands outside the normal
-// class (zero, denormal, inf, NaN, negative square-root arguments) take the
-// IEEE operation.  The reward ratio curEq / prevEq stays IEEE: a small log
+// refinement (<= 1 ulp; 8 VALU instead of 17).  A denominator or square-root
+// argument outside the normal class (zero, denormal, inf, NaN, negative
+// square-root arguments) takes the IEEE operation.  The numerator's class is
+// not looked at: a zero, infinite or NaN numerator gives the IEEE result
+// through the product, a denormal one a quotient within the 2 ulp, not the
+// IEEE bits.  The 2 ulp hold for |b| in [2^-1020, 2^1020] (1.44 measured):
+// from 2^1022 on the reciprocal is denormal and the error grows to 2.4 ulp
+// below 2^1023 and 4.0 above, still far inside the tolerance.  The shapers'
+// denominators are (a moment of log returns) + 1.19e-7 and never come near.
+// rt_sqrt holds its 1 ulp over every positive normal x (0.72 measured), and
+// perfect squares give their root exactly.  The reward ratio curEq / prevEq stays IEEE: a small log
 // reward would carry its last-bit error at a large relative size.  Every step
 // kernel uses these helpers, so the schedules stay bit-identical.
 constexpr int kNormalClass = (1 << 3) | (1 << 8);  // v_cmp_class: -normal | +normal
@@ -365,7 +383,8 @@ __device__ __forceinline__ double normal_of(const u4& x) {
 // s = (x - 1) / (x + 1) carried as s_hi + s_lo (x + 1 = u + e exactly, the
 // division's residual by fma), so the result is rounded once from a value
 // within ~2^-60 relative: it agrees with a correctly rounded log except in
-// rare last-bit cases (36 of 3e5 random ratios against glibc).  |s| < 1/63,
+// rare last-bit cases (36 of 3e5 random ratios against glibc; 0.52 ulp at
+// worst against a 200-bit log, whatever rt_div's last bits).  |s| < 1/63,
 // so the dropped s^11/11 term is < 2^-66 relative.  Elsewhere the library log.
 // Compared with the oracle (glibc log) at rtol 1e-12.
 __device__ __forceinline__ double log_ratio(double x) {
