@@ -17,7 +17,13 @@
 // share a SIMD): in iteration j the ledger waves (L) run step j's orders, the
 // generator waves (G) run step j's tick, and the finish waves (F) evaluate
 // step j-1 -- one barrier per iteration, records double-buffered by
-// iteration parity.  `done` of step j-1 is known only at the end of
+// iteration parity.  (Of step j-1 the finish waves evaluate in iteration j
+// what needs the env's lanes or feeds the pipeline: the post-tick sums,
+// equity, done, the asset fractions and the per-asset outputs.  The per-env
+// scalar chain -- reward, State.portfolio[0], shaper, episode sums -- runs
+// there too, or, at 8 lanes per env with a scalar env-log reward, is queued
+// and evaluated for 8 steps at once, one step per lane: "the reward chain
+// batched" below.)  `done` of step j-1 is known only at the end of
 // iteration j, after L and G have speculatively run step j on the assumption
 // that the episode goes on.  When F finds done (auto-reset), iteration j+1
 // rolls step j back: L resets the ledger (a fresh Broker), G restores the
@@ -308,6 +314,15 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
   __shared__ double s_disc[NST ? MGN_MAX_NSTEP : 1];                     // NST: gamma^k
   __shared__ double s_disc2[SBR ? MGN_MAX_NSTEP : 1];                     // SBR: (gamma^k)^(1/exp)
   extern __shared__ __attribute__((aligned(16))) double s_nst[];          // NST: (EPB, NPADS nst_pad(n, S))
+  // FB: the finish role batches the per-env reward chain (below, "the reward
+  // chain batched") -- one-step rewards of an 8-lane env, no window, tape or
+  // one-step-launch code.  Its queue, one entry per lane (entry i of env el at
+  // el S + i): equity after and before the step, cash less the borrowed sum,
+  // the step index; and the batch's rewards for the in-order pass
+  constexpr bool FB = S == 8 && MM == 1 && !WIN && !NST && !RP && !ONE && !K1;
+  __shared__ __attribute__((aligned(16))) double s_fqc[FB ? TW : 1], s_fqp[FB ? TW : 1], s_fqx[FB ? TW : 1],
+      s_fqr[FB ? TW : 1];
+  __shared__ int32_t s_fqk[FB ? TW : 1];
   const int role = threadIdx.x / TRIO_W;  // 0 generator, 1 ledger, 2 finish
   const int l = threadIdx.x % TRIO_W;
   // GSLOT: a handle whose assets are of several source kinds (a Composite)
@@ -371,6 +386,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
   int32_t nlen = 0, nhead = 0;                   // F (NST): NStepBuffer fill count / oldest index
   NstRun nrs{0., 0., 0., 0., 0., 0.};             // F (NRUN): the buffer's running sums, on every lane of the env
   int32_t nsl = 0;                               // F (NRUN): pops since the sums were last formed from the ring
+  int32_t fcnt = 0, fdone = 0;                   // F (FB): queued steps of the env, their done bits
   if (!kAblPro && role == 0) {
     // only the fields the kind reads (GK): TrendOU no sine phase, OU none
     constexpr bool r_sx = GK < 0 || GK == MGN_SRC_SINE || GK == MGN_SRC_SAWTOOTH || GK == MGN_SRC_TRIANGLE ||
@@ -1239,6 +1255,107 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       p.sB[(size_t)env * A + s.asset[0]] = g.shB;
     }
   };
+  // The reward chain batched (FB, and at run time a scalar env-log reward
+  // with no shaper, DSR or DDR).  A step's reward, State.portfolio[0] and
+  // shaped reward are a per-env scalar chain -- two IEEE divisions, the log,
+  // the shaper's square root and division -- that feeds nothing but outputs
+  // and the shaper's own A and B, and that all S lanes of the env would
+  // evaluate alike.  So a confirmed step only queues the chain's operands
+  // (fcnt entries, at most S: one per iteration between two flushes), and
+  // every S iterations lane i of the env evaluates queued step i: one pass of
+  // the chain for S steps.  Only the recurrences -- A, B, ep_ret, ep_len,
+  // n_done -- are replayed by every lane in step order over the batch's
+  // rewards (through LDS), lane i keeping the A and B from before step i for
+  // its shaped reward.  Every value is the per-step code's expression on the
+  // same operands, so the outputs and the state keep their bits.  A lane
+  // beyond its env's count (a rolled-back step skips an iteration, so counts
+  // differ within a wave) evaluates neutral operands and stores nothing; a
+  // padding lane (asset slot >= A) owns a queue entry like any other.  The
+  // queue is the env's own S lanes' -- one wave's -- so a flush needs no
+  // workgroup barrier; it runs in the same iteration in every finish wave.
+  // (A flush spread over the next batch's first three iterations -- rewards,
+  // recurrences, shaping and stores, a second queue buffer -- measured slower
+  // than the flush in one iteration: 466.1 against 448.5 us per 256-step
+  // launch, the per-step chain 470.1, profiles/r07_ab_finish_batch.json.)
+  const bool fbat = FB && D == 1 && !need_ar &&
+                    (p.shaper == MGN_SHAPER_NONE || p.shaper == MGN_SHAPER_DSR || p.shaper == MGN_SHAPER_DDR);
+  const auto f_wave_sync = [&]() {  // the wave's LDS writes before its reads that follow
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  const auto f_flush = [&]() {
+    if constexpr (FB) {
+      f_wave_sync();
+      const bool mine = ls < fcnt;  // the lane's entry: slot el S + ls = l
+      const double curEq = mine ? s_fqc[l] : 1., prevEq = mine ? s_fqp[l] : 1.;
+      const int k = s_fqk[l];
+      const double ratio = curEq / prevEq;
+      const double clampv = (in_kind == IN_SINGLE) ? 0.01 : 0.3;
+      const double reward = log_ratio((ratio < clampv) ? clampv : ratio);
+      double x = mine ? s_fqx[l] : 0.;
+      asm volatile("" : "+v"(x));
+      const double port0 = x / curEq;
+      s_fqr[l] = reward;
+      f_wave_sync();
+      // the recurrences, in step order
+      double r[S];
+#pragma unroll
+      for (int i = 0; i < S; ++i) r[i] = s_fqr[el * S + i];
+      double Ai = g.shA, Bi = g.shB;
+      int last = -1;  // the batch's last episode end: its epstats row
+      double st_ret = 0., st_len = 0.;
+#pragma unroll
+      for (int i = 0; i < S; ++i) {
+        if (ls == i) {
+          Ai = g.shA;
+          Bi = g.shB;
+        }
+        if (i < fcnt) {
+          const double ri = r[i];
+          if (p.shaper == MGN_SHAPER_DDR) {
+            double m = ri < 0. ? ri : 0.;
+            if (ri != ri) m = ri;
+            g.shA += p.eta * (ri - g.shA);
+            g.shB += p.eta * (m * m - g.shB);
+          } else if (p.shaper == MGN_SHAPER_DSR) {
+            g.shA += p.eta * (ri - g.shA);
+            g.shB += p.eta * (ri * ri - g.shB);
+          }
+          ep_ret += ri;
+          ep_len += 1;
+          if ((fdone >> i) & 1) {
+            st_ret = ep_ret;
+            st_len = ep_len;
+            n_done = n_done + 1;
+            last = i;
+            ep_ret = 0;
+            ep_len = 0;
+          }
+        }
+      }
+      if (last >= 0 && ls == 0) {  // episode statistics
+        MGN_G double* st = gs.epstats + (size_t)env * 4;
+        st[0] = st_ret;
+        st[1] = st_len;
+        st[2] = s_fqc[el * S + last];
+        st[3] = n_done;
+      }
+      if (!kAblNoStoreEnv && mine) {
+        double shaped_s = reward;
+        if (p.shaper == MGN_SHAPER_DDR)
+          shaped_s = clip1((0.0 + 1.0 * ddr_one_pre(reward, Ai, Bi, ddr_pre(Ai, Bi))) / 1);
+        else if (p.shaper == MGN_SHAPER_DSR)
+          shaped_s = clip1((0.0 + 1.0 * dsr_one(reward, Ai, Bi)) / 1);
+        const size_t ie = kidx(k, sN, (size_t)env);
+        if (om & O_OPT) ost(ov.obs_port + kidx(k, sNA1, bO), port0);
+        if (om & O_REW) ost(ov.reward + ie, reward);
+        if (om & O_SHP) ost(ov.shaped + ie, shaped_s);
+      }
+      fcnt = 0;
+      fdone = 0;
+    }
+  };
   drain_vmem();
   __builtin_amdgcn_s_setprio(kPrioF);
   MGN_ST(unsigned long long T0 = 0, T1 = 0, T2 = 0, acc0 = 0, acc1 = 0, Tf1 = 0, Tf2 = 0, facc[3] = {0, 0, 0};)
@@ -1312,6 +1429,45 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       const bool done = rec_done<M, S, ONE>(f.L, f.P, cashv, sh.rMl[prv][el], sh.rSh[prv][el], sh.rB[prv][el],
                                             (flags & TR_ANYMC) != 0, p, q, curEq);
       if (j == 1) MGN_IT(55, 2 * TRIO_W);
+      if (FB && fbat) {
+        // the reward chain batched: the step's chain operands queued (by the
+        // lane that will evaluate them); what needs the env's lanes or feeds
+        // the pipeline stays here -- done, the asset fractions, the per-asset
+        // stores and the step's flags
+        if (ls == fcnt) {
+          const int e = el * S + fcnt;
+          s_fqc[e] = curEq;
+          s_fqp[e] = prevEq;
+          s_fqx[e] = cashv - q.b;
+          s_fqk[e] = k;
+        }
+        fdone |= (done ? 1 : 0) << fcnt;
+        fcnt += 1;
+        MGN_ST(Tf1 = Tf2 = __builtin_amdgcn_s_memtime();)
+        if (!kAblNoStoreAsset && f.valid[0]) {
+          if (om & O_OPR) ost(ov.obs_price + kidx(k, sNF, bP), f.P[0]);
+          if (om & O_OPT) {
+            double x = f.L[0] * f.P[0];
+            asm volatile("" : "+v"(x));
+            ost(ov.obs_port + (kidx(k, sNA1, bO) + 1 + f.asset[0]), x / curEq);
+          }
+        }
+        if (!kAblNoStoreEnv && ls == 0) {
+          const size_t ie = kidx(k, sN, (size_t)env);
+          if (om & O_DONE) ost(ov.done + ie, (uint8_t)(done ? 1 : 0));
+          if (om & O_MC) {
+            const Sums qa{sh.rLpA[prv][el], q.ml, q.sh, q.b};
+            const bool mcall = (flags & TR_MCALL) && margin_call(qa, cashv, p.mainM);
+            ost(ov.margin_call + ie, (uint8_t)(mcall ? 1 : 0));
+          }
+          if (om & O_DEND) ost(ov.data_end + ie, (uint8_t)0u);
+          if (om & O_NSH) ost(ov.n_shaped + ie, (uint8_t)1);
+          if (om & O_TS) ost(ov.timestamp + ie, (uint64_t)sh.ts[prv][el]);
+        }
+        if (done && p.auto_reset) rst_out = 1;
+      } else {
+      // (the per-step chain: every other handle of these instantiations, and
+      // every other instantiation)
       const double ratio = curEq / prevEq;
       const double clampv = (in_kind == IN_SINGLE) ? 0.01 : 0.3;
       const double reward = log_ratio((ratio < clampv) ? clampv : ratio);
@@ -1580,7 +1736,11 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
           tail_rst = TAIL && K == 1;
         }
       }
+      }
     }
+    // the queued chains: every S-th iteration (at most S steps queued since
+    // the last), the same one in every finish wave
+    if (FB && fbat && j > 0 && (j & (S - 1)) == 0) f_flush();
     if (WIN && live && (flags & TR_REFILL)) {
       // a refill tick's row: the fresh Broker's portfolio on the tick's prices
       // (the sums ring_push / k_step_duo's refill record evaluate)
@@ -1629,6 +1789,9 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
     atomicAdd(&g_duo_stamps[12], facc[2]);
   })
   if constexpr (kAblEpi) return;
+  // the steps still queued (no queue survives a launch): A, B and the episode
+  // sums below are the state after the launch's last step
+  if (FB && fbat && __builtin_amdgcn_ballot_w64(fcnt > 0) != 0) f_flush();
   if (!live) return;
   if constexpr (NST != 0) {
     const double* ring = s_nst + (size_t)el * NPADS * nst_pad(p.nstep, S);
