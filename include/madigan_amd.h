@@ -36,6 +36,9 @@
  *   mgn_window_hist   of the agent loop (madigan/modelling/algorithm/
  *   mgn_rollout_window offpolicy_q.py:143, 193-194): K steps in one launch,
  *                     then every step's window
+ *   mgn_rnorm_*       the streaming reward normalisers and their reset
+ *                     (madigan/environments/reward_normalization.pyx:61-272;
+ *                     offpolicy_q.py:413-414, :428-429)
  *   mgn_get_views     zero-copy property views (env.cpp:897-913)
  *   mgn_last_error    pybind11 exception translation (DataTypes.h:36-46)
  *
@@ -52,7 +55,7 @@
 extern "C" {
 #endif
 
-#define MGN_ABI_VERSION 10
+#define MGN_ABI_VERSION 11
 #define MGN_MAX_ASSETS 64
 #define MGN_MAX_NSTEP 256
 
@@ -252,6 +255,35 @@ typedef struct {
   int32_t out_stride, out_offset;
 } mgn_ring;
 
+/* Streaming reward normaliser (madigan/environments/reward_normalization.pyx),
+ * one per env, caller-owned device memory.  kind: MGN_RNORM_*; alpha: SharpeEWMA's
+ * 2 / (window + 1), unused by the windowed kinds.
+ *   ring     (window, n_envs) slot-major: env e's std::queue<double> is slots
+ *            head, head + 1, ... (mod window) of column e (windowed kinds;
+ *            may be NULL for SharpeEWMA)
+ *   index    (3, n_envs) int64: head (front slot), size, count (count:
+ *            SortinoFixedWindowB / C and SharpeEWMA)
+ *   est      windowed kinds (2, n_envs): mean_est, ssq; SharpeEWMA (7, n_envs):
+ *            ewma, ewma_old, ewssq_old, ewssq, std_est, w1, w2
+ *   weights  SharpeEWMA: (table_len, 2) host-built {(1 - alpha) ** c, its
+ *            square} for count c = 0 .. table_len - 1 (Python-float powers, which
+ *            a device pow does not reproduce bit for bit); counts beyond the
+ *            table add 0.0, so the table ends at the first power that is 0.0
+ *   zero_var SharpeEWMA: (n_envs) sticky bytes, set where the reference's
+ *            checked division raises ZeroDivisionError (:252), cleared by
+ *            mgn_rnorm_reset */
+enum { MGN_RNORM_SHARPE_FW = 0, MGN_RNORM_SORTINO_FW_A = 1, MGN_RNORM_SORTINO_FW_B = 2,
+       MGN_RNORM_SORTINO_FW_C = 3, MGN_RNORM_SHARPE_EWMA = 4 };
+typedef struct {
+  int32_t kind, n_envs, window, table_len;
+  double alpha;
+  double *ring;
+  int64_t *index;
+  double *est;
+  const double *weights;
+  uint8_t *zero_var;
+} mgn_rnorm;
+
 typedef struct mgn_env mgn_env;
 
 int mgn_abi_version(void);
@@ -347,6 +379,24 @@ int mgn_ring_gather(const mgn_ring *ring, double *price_dev, double *port_dev, u
  * default axis -1, i.e. across the price columns): out (rows, cols - 1) =
  * in[:, 1:] - in[:, :-1] for a (rows, cols) device array */
 int mgn_feat_diff(const double *in_dev, double *out_dev, int64_t rows, int32_t cols, void *stream);
+/* RewardShaper.reset of every class (reward_normalization.pyx:87-93, :170-176,
+ * :238-246) for envs with mask_dev[e] != 0 (NULL: all): the agent's
+ * reset_state at an episode's end (modelling/algorithm/offpolicy_q.py:375);
+ * clears the envs' zero_var bytes */
+int mgn_rnorm_reset(const mgn_rnorm *rnorm, const uint8_t *mask_dev, void *stream);
+/* K x stream(reward) of every env in one launch, one lane per env
+ * (reward_normalization.pyx:95-118 SharpeFixedWindow, :135-146 SortinoFixedWindowA,
+ * :178-202 SortinoFixedWindowB, :213-218 SortinoFixedWindowC, :248-272
+ * SharpeEWMA; the agent's per-step call, offpolicy_q.py:413-414): reward_dev and
+ * out_dev (K, n_envs); out_dev may be reward_dev.  done_dev (K, n_envs) or
+ * NULL: env e is reset after step k where done_dev[k, e] != 0, its terminal
+ * reward streamed first (offpolicy_q.py:428-429).  Bit-identical to the
+ * compiled reference per env.  A SharpeEWMA step of zero variance writes NaN,
+ * advances the statistics and sets zero_var[e].  MGN_ERR_CONFIG: a null
+ * descriptor or array, k_steps < 1, n_envs < 1, an unknown kind, window < 2
+ * (the reference's window-1 forms divide by zero). */
+int mgn_rnorm_stream(const mgn_rnorm *rnorm, const double *reward_dev, const uint8_t *done_dev,
+                     double *out_dev, int32_t k_steps, void *stream);
 /* Lane layout of the step kernels: assets held per lane (1, 2, 4, 8; 0 =
  * automatic, the default).  Results are bit-identical for every layout (the
  * canonical reduction tree does not depend on it); only speed changes. */

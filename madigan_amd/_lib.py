@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmadigan_hip.so")
 MAX_ASSETS = 64
-ABI_VERSION = 10
+ABI_VERSION = 11
 SRC_PARAMS = 64
 AUX_WIDTH = 24
 MAX_NSTEP = 256
@@ -30,6 +30,8 @@ REWARD_ENV_LOG, REWARD_AGENT_SUM, REWARD_AGENT_PER_ASSET = range(3)
 (NORM_NONE, NORM_LOG, NORM_LOOKBACK, NORM_STANDARD_NORMAL, NORM_LOOKBACK_LOG,
  NORM_LOG_STANDARD_NORMAL) = range(6)
 RING_PLAIN, RING_PAIR_RATIO = range(2)
+(RNORM_SHARPE_FW, RNORM_SORTINO_FW_A, RNORM_SORTINO_FW_B, RNORM_SORTINO_FW_C,
+ RNORM_SHARPE_EWMA) = range(5)
 STEP_NONE, STEP_UNITS, STEP_SINGLE = range(3)
 SCHED_AUTO, SCHED_SINGLE, SCHED_DUO, SCHED_TRIO = range(4)
 OP_BROKER_UNITS, OP_BROKER_SINGLE, OP_BROKER_CLOSE, OP_PORT_TXN, OP_PORT_CLOSE, OP_CHECK_ORDER = range(6)
@@ -99,6 +101,12 @@ class Ring(C.Structure):
                 ("len", C.c_void_p), ("out_stride", C.c_int32), ("out_offset", C.c_int32)]
 
 
+class RNorm(C.Structure):  # mgn_rnorm
+    _fields_ = [("kind", C.c_int32), ("n_envs", C.c_int32), ("window", C.c_int32), ("table_len", C.c_int32),
+                ("alpha", C.c_double), ("ring", C.c_void_p), ("index", C.c_void_p), ("est", C.c_void_p),
+                ("weights", C.c_void_p), ("zero_var", C.c_void_p)]
+
+
 SYMBOLS = {
     # name: (restype, argtypes)
     "mgn_abi_version": (C.c_int, []),
@@ -136,6 +144,8 @@ SYMBOLS = {
     "mgn_ring_clear": (C.c_int, [C.POINTER(Ring), C.c_void_p, C.c_void_p]),
     "mgn_ring_gather": (C.c_int, [C.POINTER(Ring), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgn_feat_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "mgn_rnorm_reset": (C.c_int, [C.POINTER(RNorm), C.c_void_p, C.c_void_p]),
+    "mgn_rnorm_stream": (C.c_int, [C.POINTER(RNorm), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mgn_set_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "mgn_get_layout": (C.c_int, [C.c_void_p]),
     "mgn_set_schedule": (C.c_int, [C.c_void_p, C.c_int32]),

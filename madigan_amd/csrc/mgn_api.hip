@@ -18,6 +18,7 @@
 #include "../../include/madigan_amd.h"
 #include "mgn_aux_kernels.h"
 #include "mgn_launch.h"
+#include "mgn_rnorm.h"
 
 namespace {
 
@@ -1030,6 +1031,40 @@ int mgn_feat_diff(const double* in_dev, double* out_dev, int64_t rows, int32_t c
   hipLaunchKernelGGL(mgn::k_feat_diff, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, in_dev, out_dev, rows, (int)cols);
   return check_hip(nullptr, hipGetLastError(), "mgn_feat_diff");
+}
+
+static int rnorm_ok(const mgn_rnorm* r) {
+  if (!r) return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser");
+  if (r->kind < MGN_RNORM_SHARPE_FW || r->kind > MGN_RNORM_SHARPE_EWMA)
+    return fail(nullptr, MGN_ERR_CONFIG, "unknown reward normaliser kind");
+  if (r->n_envs < 1) return fail(nullptr, MGN_ERR_CONFIG, "reward normaliser: n_envs must be >= 1");
+  // window 1: the reference's windowed stream divides by an emptied queue's
+  // size, its EWMA by w1 - w2 / w1 = 0
+  if (r->window < 2) return fail(nullptr, MGN_ERR_CONFIG, "reward normaliser: window must be >= 2");
+  if (!r->index || !r->est) return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser state");
+  if (r->kind == MGN_RNORM_SHARPE_EWMA) {
+    if (!r->zero_var || (r->table_len > 0 && !r->weights) || r->table_len < 0)
+      return fail(nullptr, MGN_ERR_CONFIG, "null SharpeEWMA weight table or zero-variance bytes");
+  } else if (!r->ring) {
+    return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser ring");
+  }
+  return MGN_OK;
+}
+
+int mgn_rnorm_reset(const mgn_rnorm* r, const uint8_t* mask_dev, void* stream) {
+  int rc = rnorm_ok(r);
+  if (rc != MGN_OK) return rc;
+  return check_hip(nullptr, (hipError_t)mgn::rnorm_launch_reset(*r, mask_dev, stream), "mgn_rnorm_reset");
+}
+
+int mgn_rnorm_stream(const mgn_rnorm* r, const double* reward_dev, const uint8_t* done_dev, double* out_dev,
+                     int32_t k_steps, void* stream) {
+  int rc = rnorm_ok(r);
+  if (rc != MGN_OK) return rc;
+  if (!reward_dev || !out_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: null reward or output");
+  if (k_steps < 1) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: k_steps must be >= 1");
+  return check_hip(nullptr, (hipError_t)mgn::rnorm_launch_stream(*r, reward_dev, done_dev, out_dev, k_steps, stream),
+                   "mgn_rnorm_stream");
 }
 
 int mgn_set_layout(mgn_env* e, int32_t assets_per_lane) {

@@ -28,7 +28,8 @@ def main():
     # the translation units rebuilt with the extra flags (MGN_VARIANT_UNITS,
     # comma-separated unit suffixes: default 8t, the C3 headline's unit)
     units = os.environ.get("MGN_VARIANT_UNITS", "8t").split(",")
-    redo = {"mgn_api.hip"} | {f"mgn_launch_a{u}.hip" for u in units}
+    # (an entry ending in .hip names a unit outright, e.g. mgn_rnorm.hip)
+    redo = {"mgn_api.hip"} | {u if u.endswith(".hip") else f"mgn_launch_a{u}.hip" for u in units}
 
     def one(src):
         base = os.path.basename(src)
