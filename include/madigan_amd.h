@@ -39,6 +39,9 @@
  *   mgn_rnorm_*       the streaming reward normalisers and their reset
  *                     (madigan/environments/reward_normalization.pyx:61-272;
  *                     offpolicy_q.py:413-414, :428-429)
+ *   mgn_xbuf_*        the uniform experience replay buffer fed from a launch
+ *                     (madigan/utils/buffers/replay_buffer.py:23-172 over
+ *                     nstep_buffer.py:315-376; offpolicy_q.py:196-207)
  *   mgn_get_views     zero-copy property views (env.cpp:897-913)
  *   mgn_last_error    pybind11 exception translation (DataTypes.h:36-46)
  *
@@ -284,6 +287,70 @@ typedef struct {
   uint8_t *zero_var;
 } mgn_rnorm;
 
+/* Uniform experience replay on the device (madigan/utils/buffers/
+ * replay_buffer.py:23-172), fed from a launch's outputs and launch history,
+ * caller-owned device memory.  mgn_xbuf, mgn_xbuf_batch and the mgn_xbuf_*
+ * entry points are new symbols only: no existing struct or function changed,
+ * so MGN_ABI_VERSION stays 11.
+ *   n_envs, n_assets (A), n_feats (F), window (W >= 1), nstep (n, 1..255),
+ *   reward_dim (D: 1 or A) the feeding handle's dimensions
+ *   state_f32    0: windows stored as float64; 1: rounded to nearest float32
+ *                (prep_state_tensors casts them anyway).  Timestamps, actions,
+ *                rewards and flags keep their types
+ *   plan_steps   steps per launch the plan arrays hold (k_steps <= plan_steps)
+ *   size         slots (ReplayBuffer.size)
+ *   state_price (size, W, F), state_port (size, W, A+1), state_ts (size, W),
+ *   next_price / next_port / next_ts likewise: SARSD.state / .next_state,
+ *                zero-padded below W rows as mgn_window_hist pads them
+ *   action       (size, A) int64   SARSD.action: the step's discrete atoms
+ *   reward       (size, D)         the n-step shaped reward of the pop
+ *   done         (size)
+ *   cursor       (2) int64 {current_idx, filled} (replay_buffer.py:38-39)
+ *   pending      (n_envs) int32: entries in env e's NStepBuffer (its len())
+ *   carry_rows   (n_envs, max(n-1, 1), F+A+1), carry_ts (n_envs, max(n-1, 1)):
+ *                the n - 1 history rows below the current window's W-row
+ *                frame, which the states of pending entries still reach
+ *   carry_act    (n_envs, max(n-1, 1), A) int8, carry_fill (n_envs, max(n-1, 1))
+ *                int32: the action and the state's fill of the last n - 1
+ *                steps (the pending entries are the newest `pending` of them)
+ *   plan         (2, plan_steps * n_envs) int32 scratch of one add: per (step,
+ *                env) the pending count, and the exclusive scan of the pops
+ *   plan_base    (1) int64 scratch: current_idx when the add began */
+typedef struct {
+  int32_t n_envs, n_assets, n_feats, window, nstep, reward_dim, state_f32, plan_steps;
+  int64_t size;
+  void *state_price, *state_port;
+  int64_t *state_ts;
+  void *next_price, *next_port;
+  int64_t *next_ts;
+  int64_t *action;
+  double *reward;
+  uint8_t *done;
+  int64_t *cursor;
+  int32_t *pending;
+  double *carry_rows;
+  int64_t *carry_ts;
+  int8_t *carry_act;
+  int32_t *carry_fill;
+  int32_t *plan;
+  int64_t *plan_base;
+} mgn_xbuf;
+
+/* a collated SARSD batch (replay_buffer.py:109-132), caller-owned device
+ * memory: state_* / next_* (B, W, F), (B, W, A+1) in the buffer's state type
+ * and (B, W) int64; action (B, A) int64; reward (B, D); done (B); idx (B)
+ * int64, the slot of each row (-1: none).  Any pointer may be NULL. */
+typedef struct {
+  void *state_price, *state_port;
+  int64_t *state_ts;
+  void *next_price, *next_port;
+  int64_t *next_ts;
+  int64_t *action;
+  double *reward;
+  uint8_t *done;
+  int64_t *idx;
+} mgn_xbuf_batch;
+
 typedef struct mgn_env mgn_env;
 
 int mgn_abi_version(void);
@@ -336,7 +403,9 @@ int mgn_window(mgn_env *env, double *price_dev, double *port_dev, uint64_t *ts_d
  * every ring push of the launch in a handle-owned history (W + K*(W+1) rows
  * per env, allocated on first use); mgn_window_hist then writes all K windows
  * to (K,N,W,F) / (K,N,W,A+1) / (K,N,W) caller buffers (any may be NULL;
- * element-wise normalisers only).  mgn_rollout_window: per_step 1 = both;
+ * element-wise normalisers only; an even window length, as it stores row
+ * pairs -- an odd window's history serves mgn_window_hist_view and
+ * mgn_xbuf_add).  mgn_rollout_window: per_step 1 = both;
  * per_step 0 = mgn_rollout + mgn_window (the last window only). */
 int mgn_rollout_hist(mgn_env *env, const int8_t *actions_dev, int32_t k_steps, const mgn_traj *out);
 int mgn_window_hist(mgn_env *env, double *price_dev, double *port_dev, uint64_t *ts_dev);
@@ -397,6 +466,52 @@ int mgn_rnorm_reset(const mgn_rnorm *rnorm, const uint8_t *mask_dev, void *strea
  * (the reference's window-1 forms divide by zero). */
 int mgn_rnorm_stream(const mgn_rnorm *rnorm, const double *reward_dev, const uint8_t *done_dev,
                      double *out_dev, int32_t k_steps, void *stream);
+/* K x ReplayBuffer.add of every env in one call (replay_buffer.py:68-90 with
+ * NStepBuffer.pop_nstep_sarsd, nstep_buffer.py:342-361; the agent's
+ * self.buffer.add(sarsd), offpolicy_q.py:196-203), fed from a launch:
+ *   hist, hist_ts, hend, hlen  the launch history (mgn_hist_view; W + K * (W + 1)
+ *                              rows per env)
+ *   len0 (n_envs) int32        every env's window fill before the launch
+ *                              (views.ring_len then)
+ *   actions (K, n_envs, A) int8, done (K, n_envs), shaped (K, n_envs, n[, A]),
+ *   n_shaped (K, n_envs)       the launch's input and outputs (mgn_traj)
+ * Pop j < n_shaped[k, e] of step k of env e becomes one transition: state =
+ * the window before its origin step k - (p - 1) + j (p: the env's pending
+ * entries at step k), action = that step's, reward = shaped[k, e, j],
+ * next_state = the window after step k (the terminal window when done[k, e]),
+ * done = done[k, e].  Slots are handed out from current_idx in the order step,
+ * env, pop by an exclusive scan of n_shaped (no atomics: the order is
+ * deterministic); filled saturates at size.  Runs on `stream`, does not
+ * synchronise the host.  MGN_ERR_CONFIG before any HIP call: a null
+ * descriptor, array or storage pointer, window < 1, nstep outside 1..255
+ * (n_shaped is a byte), reward_dim not 1 or n_assets, k_steps < 1 or >
+ * plan_steps, size < (k_steps + nstep - 1) * n_envs (a launch must not
+ * overwrite its own slots). */
+int mgn_xbuf_add(const mgn_xbuf *xbuf, const double *hist_dev, const uint64_t *hist_ts_dev,
+                 const int32_t *hend_dev, const int32_t *hlen_dev, const int32_t *len0_dev,
+                 const int8_t *actions_dev, const uint8_t *done_dev, const double *shaped_dev,
+                 const uint8_t *n_shaped_dev, int32_t k_steps, void *stream);
+/* ReplayBuffer.sample (replay_buffer.py:92-107, _sample :109-132): n_batch
+ * indices uniform in [0, filled), drawn on the device from Philox4x32-10 keyed
+ * by seed with counter (call, draw index) as floor(x * filled / 2^64) of a
+ * 64-bit draw x, then the collated batch of those slots.  filled == 0 writes
+ * idx = -1 and zeros.  MGN_ERR_CONFIG: a bad descriptor, a null batch,
+ * n_batch < 1. */
+int mgn_xbuf_sample(const mgn_xbuf *xbuf, const mgn_xbuf_batch *batch, int64_t n_batch, uint64_t seed,
+                    uint64_t call, void *stream);
+/* ReplayBuffer._sample(idxs) (replay_buffer.py:109-132; get_full :148-149,
+ * get_latest :151-152): the collated batch of the slots idx_dev (n_batch)
+ * int64; an index outside [0, filled) gives idx = -1 and zeros */
+int mgn_xbuf_gather(const mgn_xbuf *xbuf, const int64_t *idx_dev, const mgn_xbuf_batch *batch,
+                    int64_t n_batch, void *stream);
+/* nstep_only 0: ReplayBuffer.clear (replay_buffer.py:154-159): cursor and
+ * pending entries; 1: clear_nstep (:161-162): the pending entries only.
+ * `pending` mirrors the handle's n-step rings (views.nstep_len), which
+ * mgn_reset keeps: the caller zeroes those too before the next add, or the
+ * launch pops entries the buffer no longer holds.  An add counts a step's
+ * pops as min(n_shaped, pending at the step), in the scan and in the copy
+ * alike, so no slot is counted as filled and left unwritten. */
+int mgn_xbuf_clear(const mgn_xbuf *xbuf, int32_t nstep_only, void *stream);
 /* Lane layout of the step kernels: assets held per lane (1, 2, 4, 8; 0 =
  * automatic, the default).  Results are bit-identical for every layout (the
  * canonical reduction tree does not depend on it); only speed changes. */

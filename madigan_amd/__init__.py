@@ -12,10 +12,11 @@ from .config import ConfigError, SourceSpec, replay_spec, spec_from_config
 from .env import (Asset, BatchedEnv, BrokerResponse, DataSourceTick, Env, EnvInfo, RiskInfo, State,
                   get_env_info, make_batched_env, make_env)
 from .hdf import HDFSourceSingle, write_hdf
+from .replay_buffer import DeviceReplayBuffer
 from .preprocessor import (MultiStackerDiscrete, PreProcessor, StackerDiscrete, StackerDiscretePairs,
                            StackerDiscreteReturns, make_preprocessor)
 
-__all__ = ["Asset", "BatchedEnv", "BrokerResponse", "ConfigError", "DataSourceTick", "Env",
+__all__ = ["Asset", "BatchedEnv", "BrokerResponse", "ConfigError", "DataSourceTick", "DeviceReplayBuffer", "Env",
            "EnvInfo", "HDFSourceSingle", "PreProcessor", "RiskInfo", "SourceSpec",
            "StackerDiscrete", "State", "get_env_info", "make_batched_env", "make_env",
            "make_preprocessor", "MultiStackerDiscrete", "StackerDiscretePairs",

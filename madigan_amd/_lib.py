@@ -107,6 +107,22 @@ class RNorm(C.Structure):  # mgn_rnorm
                 ("weights", C.c_void_p), ("zero_var", C.c_void_p)]
 
 
+class XBuf(C.Structure):  # mgn_xbuf
+    _fields_ = [(n, C.c_int32) for n in ("n_envs", "n_assets", "n_feats", "window", "nstep", "reward_dim",
+                                         "state_f32", "plan_steps")] + [("size", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("state_price", "state_port", "state_ts", "next_price", "next_port", "next_ts",
+                                  "action", "reward", "done", "cursor", "pending", "carry_rows", "carry_ts",
+                                  "carry_act", "carry_fill", "plan", "plan_base")]
+
+
+XBUF_BATCH_FIELDS = ("state_price", "state_port", "state_ts", "next_price", "next_port", "next_ts", "action",
+                     "reward", "done", "idx")
+
+
+class XBufBatch(C.Structure):  # mgn_xbuf_batch
+    _fields_ = [(n, C.c_void_p) for n in XBUF_BATCH_FIELDS]
+
+
 SYMBOLS = {
     # name: (restype, argtypes)
     "mgn_abi_version": (C.c_int, []),
@@ -146,6 +162,11 @@ SYMBOLS = {
     "mgn_feat_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "mgn_rnorm_reset": (C.c_int, [C.POINTER(RNorm), C.c_void_p, C.c_void_p]),
     "mgn_rnorm_stream": (C.c_int, [C.POINTER(RNorm), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mgn_xbuf_add": (C.c_int, [C.POINTER(XBuf)] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]),
+    "mgn_xbuf_sample": (C.c_int, [C.POINTER(XBuf), C.POINTER(XBufBatch), C.c_int64, C.c_uint64, C.c_uint64,
+                                  C.c_void_p]),
+    "mgn_xbuf_gather": (C.c_int, [C.POINTER(XBuf), C.c_void_p, C.POINTER(XBufBatch), C.c_int64, C.c_void_p]),
+    "mgn_xbuf_clear": (C.c_int, [C.POINTER(XBuf), C.c_int32, C.c_void_p]),
     "mgn_set_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "mgn_get_layout": (C.c_int, [C.c_void_p]),
     "mgn_set_schedule": (C.c_int, [C.c_void_p, C.c_int32]),

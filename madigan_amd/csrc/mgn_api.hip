@@ -19,6 +19,7 @@
 #include "mgn_aux_kernels.h"
 #include "mgn_launch.h"
 #include "mgn_rnorm.h"
+#include "mgn_xbuf.h"
 
 namespace {
 
@@ -802,7 +803,6 @@ int mgn_rollout_hist(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, con
   if (!actions_dev || !out) return fail(e, MGN_ERR_ARG, "null actions/out");
   if (k_steps < 1) return fail(e, MGN_ERR_LENGTH, "k_steps must be >= 1");
   if (e->W == 0) return fail(e, MGN_ERR_CONFIG, "handle has no window (window_length = 0)");
-  if (e->W % 2) return fail(e, MGN_ERR_CONFIG, "the launch history needs an even window length");
   if (k_steps > mgn::HIST_KMAX) return fail(e, MGN_ERR_LENGTH, "the launch history holds at most 64 steps");
   if (need_tape(e) != MGN_OK) return MGN_ERR_CONFIG;
   const int C = e->F + e->A + 1;
@@ -847,6 +847,8 @@ int mgn_rollout_hist(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, con
 int mgn_window_hist(mgn_env* e, double* price_dev, double* port_dev, uint64_t* ts_dev) {
   if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
   auto& hb = e->hb[e->hcur];
+  // (k_hist_gather stores row pairs; the history itself takes any window)
+  if (e->W % 2) return fail(e, MGN_ERR_CONFIG, "the launch history needs an even window length");
   if (hb.k == 0) return fail(e, MGN_ERR_CONFIG, "no mgn_rollout_hist to gather from");
   if (!price_dev && !port_dev && !ts_dev) return MGN_OK;
   const int C = e->F + e->A + 1;
@@ -911,6 +913,7 @@ int mgn_rollout_window(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, c
   if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
   if (per_step) {
     if (!price_dev || !port_dev) return fail(e, MGN_ERR_ARG, "per_step windows need caller price/port buffers");
+    if (e->W % 2) return fail(e, MGN_ERR_CONFIG, "the launch history needs an even window length");
     const int st = mgn_rollout_hist(e, actions_dev, k_steps, out);
     return st != MGN_OK ? st : mgn_window_hist(e, price_dev, port_dev, ts_dev);
   }
@@ -1065,6 +1068,76 @@ int mgn_rnorm_stream(const mgn_rnorm* r, const double* reward_dev, const uint8_t
   if (k_steps < 1) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: k_steps must be >= 1");
   return check_hip(nullptr, (hipError_t)mgn::rnorm_launch_stream(*r, reward_dev, done_dev, out_dev, k_steps, stream),
                    "mgn_rnorm_stream");
+}
+
+static int xbuf_ok(const mgn_xbuf* x) {
+  if (!x) return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer");
+  if (x->n_envs < 1 || x->n_assets < 1 || x->n_feats < 1)
+    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: n_envs, n_assets and n_feats must be >= 1");
+  if (x->window < 1) return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: window must be >= 1");
+  if (x->nstep < 1 || x->nstep > 255)
+    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: nstep must be 1..255 (n_shaped is a byte)");
+  if (x->reward_dim != 1 && x->reward_dim != x->n_assets)
+    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: reward_dim must be 1 or n_assets");
+  if (x->size < 1) return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: size must be >= 1");
+  if (!x->state_price || !x->state_port || !x->state_ts || !x->next_price || !x->next_port || !x->next_ts ||
+      !x->action || !x->reward || !x->done)
+    return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer storage");
+  if (!x->cursor || !x->pending) return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer cursor or pending counts");
+  return MGN_OK;
+}
+
+int mgn_xbuf_add(const mgn_xbuf* x, const double* hist_dev, const uint64_t* hist_ts_dev, const int32_t* hend_dev,
+                 const int32_t* hlen_dev, const int32_t* len0_dev, const int8_t* actions_dev, const uint8_t* done_dev,
+                 const double* shaped_dev, const uint8_t* n_shaped_dev, int32_t k_steps, void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!hist_dev || !hist_ts_dev || !hend_dev || !hlen_dev || !len0_dev || !actions_dev || !done_dev || !shaped_dev ||
+      !n_shaped_dev)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: null launch array");
+  if (!x->carry_rows || !x->carry_ts || !x->carry_act || !x->carry_fill || !x->plan || !x->plan_base)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: null carry or plan arrays");
+  if (k_steps < 1 || k_steps > x->plan_steps)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: k_steps must be 1..plan_steps");
+  if (x->size < ((int64_t)k_steps + x->nstep - 1) * x->n_envs)
+    return fail(nullptr, MGN_ERR_CONFIG,
+                "mgn_xbuf_add: size must be >= (k_steps + nstep - 1) * n_envs (a launch must not overwrite its own slots)");
+  const int64_t hrows = (int64_t)x->window + (int64_t)k_steps * (x->window + 1);
+  if ((int64_t)k_steps * x->n_envs >= ((int64_t)1 << 31) || hrows >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: launch exceeds 2^31 (step, env) pairs");
+  mgn::XbLaunch l;
+  l.hist = hist_dev; l.hist_ts = (const int64_t*)hist_ts_dev; l.hend = hend_dev; l.hlen = hlen_dev;
+  l.len0 = len0_dev; l.actions = actions_dev; l.done = done_dev; l.shaped = shaped_dev; l.n_shaped = n_shaped_dev;
+  l.K = k_steps; l.hrows = (int32_t)hrows;
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_add(*x, l, stream), "mgn_xbuf_add");
+}
+
+int mgn_xbuf_sample(const mgn_xbuf* x, const mgn_xbuf_batch* batch, int64_t n_batch, uint64_t seed, uint64_t call,
+                    void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!batch) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_sample: null batch");
+  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_sample: n_batch must be 1..2^31-1");
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather(*x, nullptr, *batch, n_batch, seed, call, stream),
+                   "mgn_xbuf_sample");
+}
+
+int mgn_xbuf_gather(const mgn_xbuf* x, const int64_t* idx_dev, const mgn_xbuf_batch* batch, int64_t n_batch,
+                    void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!batch || !idx_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather: null batch or indices");
+  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather: n_batch must be 1..2^31-1");
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather(*x, idx_dev, *batch, n_batch, 0, 0, stream),
+                   "mgn_xbuf_gather");
+}
+
+int mgn_xbuf_clear(const mgn_xbuf* x, int32_t nstep_only, void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_clear(*x, nstep_only, stream), "mgn_xbuf_clear");
 }
 
 int mgn_set_layout(mgn_env* e, int32_t assets_per_lane) {

@@ -357,6 +357,16 @@ class BatchedEnv:
             ptr = C.c_void_p(m.data_ptr())
         L.check(self.lib.mgn_reset(self.h, ptr), self.h)
 
+    def clear_nstep(self):
+        """NStepBuffer.clear (nstep_buffer.py:372-373) for every env: the
+        pending n-step entries go.  `reset()` keeps them, as the reference's
+        Env.reset knows nothing of the agent's n-step buffer."""
+        torch = _torch()
+        if self.nstep > 1:
+            with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+                self._t(self._v.nstep_len, torch.int32, (self.N,)).zero_()
+                self._t(self._v.nstep_head, torch.int32, (self.N,)).zero_()
+
     def step(self, units=None, asset_idx=None) -> StepOutput:
         """Env::step() (units None), step(units (N,A)) or step(asset_idx (N), units (N))."""
         torch = _torch()
@@ -490,14 +500,21 @@ class BatchedEnv:
             tc.pop(next(iter(tc)))
         return t
 
-    def rollout(self, actions, out: Optional[dict] = None) -> dict:
-        """K fused steps from discrete actions (K,N,A) int8 via action_to_transaction."""
+    def launch_actions(self, actions):
+        """A launch's discrete actions as the entry points read them: a
+        contiguous (K, N, A) int8 tensor on the handle's device (the argument
+        itself when it already is one)."""
         torch = _torch()
         if not (isinstance(actions, torch.Tensor) and actions.device == self.device
                 and actions.dtype == torch.int8 and actions.is_contiguous()):
             actions = torch.as_tensor(actions).to(self.device, torch.int8).contiguous()
         if actions.dim() != 3 or actions.shape[1] != self.N or actions.shape[2] != self.A:
             raise ValueError(f"actions must be (K, {self.N}, {self.A}), got {tuple(actions.shape)}")
+        return actions
+
+    def rollout(self, actions, out: Optional[dict] = None) -> dict:
+        """K fused steps from discrete actions (K,N,A) int8 via action_to_transaction."""
+        actions = self.launch_actions(actions)
         K = int(actions.shape[0])
         own = out is None
         out = self.alloc_traj(K) if own else out
@@ -648,11 +665,7 @@ class BatchedEnv:
         torch = _torch()
         if not self.W:
             raise RuntimeError("env built with window=0")
-        if not (isinstance(actions, torch.Tensor) and actions.device == self.device
-                and actions.dtype == torch.int8 and actions.is_contiguous()):
-            actions = torch.as_tensor(actions).to(self.device, torch.int8).contiguous()
-        if actions.dim() != 3 or actions.shape[1] != self.N or actions.shape[2] != self.A:
-            raise ValueError(f"actions must be (K, {self.N}, {self.A}), got {tuple(actions.shape)}")
+        actions = self.launch_actions(actions)
         K = int(actions.shape[0])
         out = self.alloc_traj(K) if out is None else out
         self._check_traj(out, K)
@@ -669,6 +682,20 @@ class BatchedEnv:
         L.check(self.lib.mgn_rollout_window(self.h, C.c_void_p(actions.data_ptr()), K, C.byref(t),
                                             *ptrs, int(per_step)), self.h)
         return out, win
+
+    def rollout_hist(self, actions, out: Optional[dict] = None) -> dict:
+        """`rollout(actions)` that also keeps every ring push of the launch in
+        the handle's launch history (mgn_rollout_hist), for `window_hist_view()`
+        and `DeviceReplayBuffer.add_launch`; any window length."""
+        if not self.W:
+            raise RuntimeError("env built with window=0")
+        actions = self.launch_actions(actions)
+        K = int(actions.shape[0])
+        own = out is None
+        out = self.alloc_traj(K) if own else out
+        t = self._traj_for(out, K, cache=not own)
+        L.check(self.lib.mgn_rollout_hist(self.h, C.c_void_p(actions.data_ptr()), K, C.byref(t)), self.h)
+        return out
 
     def window_hist_view(self) -> dict:
         """The last mgn_rollout_hist's launch history, read in place
