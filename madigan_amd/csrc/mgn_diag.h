@@ -11,7 +11,8 @@
      defined(MGN_ABL_NOSTORE_ASSET) || defined(MGN_ABL_NOSTORE_ENV) || defined(MGN_ABL_DRAW) ||          \
      defined(MGN_TRIO_ABL_PRO) || defined(MGN_TRIO_ABL_G) || defined(MGN_TRIO_ABL_L) ||                  \
      defined(MGN_TRIO_ABL_F) || defined(MGN_TRIO_ABL_EPI) || defined(MGN_NST_ABL_TERM) ||                \
-     defined(MGN_NST_ABL_SUM) || defined(MGN_NST_ABL_ROW) || defined(MGN_NO_GK))
+     defined(MGN_NST_ABL_SUM) || defined(MGN_NST_ABL_ROW) || defined(MGN_NO_GK) ||                      \
+     defined(MGN_ABL_PLAIN_OFF))
 #error "stamp / ablation switches belong to diagnostic builds (-DMGN_DIAG, tools/build_variant.py)"
 #endif
 
@@ -77,11 +78,34 @@ constexpr bool kAblNoStoreEnv = true;    // no per-env output stores
 #else
 constexpr bool kAblNoStoreEnv = false;
 #endif
+#ifdef MGN_ABL_PLAIN_OFF
+constexpr bool kAblPlainOff = true;      // broker_spec: every wave runs the general passes (right values)
+#else
+constexpr bool kAblPlainOff = false;
+#endif
 
 #ifdef MGN_STAMPS
 // diagnostic build only: per role, cycles of [work 1, wait A, work 2, wait B]
 // summed over one wave per role and block, then the iteration count
 __device__ unsigned long long g_duo_stamps[24];
+// k_step_trio: the same [work, wait] cycles kept apart by the parity of the
+// iteration j -- [4 r + 2 (j & 1) + {0 work, 1 wait}], r = 0 generator, 1
+// ledger, 2 finish; [12] / [13]: the generator's even / odd iterations that
+// began on an even draw index (timestamp + resets, mgn_math.h v3: the whole
+// Box-Muller transform of a pair runs on its even draw), [14] / [15]: its
+// even / odd iterations
+__device__ unsigned long long g_trio_par[16];
+// MGN_PAR(acc, j, work, wait): acc[2 (j & 1)] += work, acc[2 (j & 1) + 1] += wait
+// (selects, no runtime index into the registers)
+#define MGN_PAR(acc, j, work, wait)                      \
+  {                                                      \
+    const unsigned long long w_ = (work), a_ = (wait);   \
+    const bool o_ = ((j) & 1) != 0;                      \
+    acc[0] += o_ ? 0 : w_;                               \
+    acc[1] += o_ ? 0 : a_;                               \
+    acc[2] += o_ ? w_ : 0;                               \
+    acc[3] += o_ ? a_ : 0;                               \
+  }
 // per-block sub-phase accumulators, one writer (the block's first ledger lane)
 __shared__ unsigned long long s_duo_sub[8];
 // wall clock (s_memrealtime, 100 MHz) per block (first 2048 blocks), plain

@@ -445,8 +445,12 @@ __device__ __forceinline__ void duo_store(const DuoRec<S>& sh, const Lane<1>& s,
 // replaced one select per order).  M orders per lane (two-slot
 // layout): the lane's orders in slot order within its step.  c_own[m]: the
 // cash before the lane's order m; cend: after the last order (the segment's
-// last lane's)
-template <int S, int M>
+// last lane's).
+// PLAIN (broker_spec's plain wave): every order of the wave has X1 == -0.0
+// and Z == +0.0 by their bits, so the step is c - y alone: x + (-0.0) == x
+// and x - (+0.0) == x for every x, signed zeros included, and a NaN cash
+// still passes through c - y as it does through the general form
+template <int S, int M, bool PLAIN = false>
 __device__ __forceinline__ void dpp_chain(double cash0, const OwnChk (&own)[M], const bool (&gown)[M], int ls,
                                           double (&c_own)[M], double& cend) {
   double X1[M], y[M], Z[M];
@@ -460,7 +464,8 @@ __device__ __forceinline__ void dpp_chain(double cash0, const OwnChk (&own)[M], 
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       mid[m] = c;
-      c = ((c + X1[m]) - y[m]) - Z[m];
+      if constexpr (PLAIN) c = c - y[m];
+      else c = ((c + X1[m]) - y[m]) - Z[m];
     }
     return c;
   };
@@ -489,25 +494,31 @@ __device__ __forceinline__ void dpp_chain(double cash0, const OwnChk (&own)[M], 
 // the sums after every executed order.
 // ONE (a one-asset env on S = 2 lanes): the tree is lane 0's one leaf; every
 // lane of the segment takes lane 0's root (its path is only read by lane 0,
-// whose order is the only one)
-template <int S, bool ONE = false>
+// whose order is the only one).
+// NQ < 4 (broker_spec's plain wave): only the first NQ sums are formed; the
+// leaves of the others are +0.0 in every lane of the wave, before and after
+// the orders, and a tree of +0.0 leaves sums to +0.0 under every guess, so
+// their paths and roots are +0.0 without the additions
+template <int S, bool ONE = false, int NQ = 4>
 __device__ __forceinline__ void dpp_tree4(const double (&pre)[4], const double (&post)[4], bool go_own, int ls,
                                           double (&path)[4], double (&rootP)[4]) {
-  double nP[4], nQ[4];
+  double nP[NQ], nQ[NQ];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
+  for (int q = 0; q < NQ; ++q) {
     path[q] = pre[q];
     nQ[q] = pre[q];
     nP[q] = go_own ? post[q] : pre[q];
   }
+#pragma unroll
+  for (int q = NQ; q < 4; ++q) path[q] = rootP[q] = 0.0;
   if constexpr (ONE) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) rootP[q] = seg_bcast<S, 0>(nP[q]);
+    for (int q = 0; q < NQ; ++q) rootP[q] = seg_bcast<S, 0>(nP[q]);
     return;
   }
   auto level = [&](auto sibP, auto sibQ, bool right) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NQ; ++q) {
       const double sp = sibP(nP[q]), sq = sibQ(nQ[q]);
       path[q] = path[q] + (right ? sp : sq);
       nP[q] = nP[q] + sp;
@@ -523,55 +534,26 @@ __device__ __forceinline__ void dpp_tree4(const double (&pre)[4], const double (
   if constexpr (S >= 16)
     level([](double v) { return dpp_f64<0x140>(v); }, [](double v) { return dpp_f64<0x140>(v); }, (ls & 8) != 0);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) rootP[q] = nP[q];
+  for (int q = 0; q < NQ; ++q) rootP[q] = nP[q];
 }
 
-// Broker::handleTransaction(units) for a segment of S lanes, one asset per
-// lane, resolved speculatively.  The serial dependency between orders (each
-// risk check sees the cash and portfolio sums the earlier orders left,
-// Broker.cpp:149-155) is only a dependency on which earlier orders executed.
-// Guess that every nonzero order executes; then each lane checks ITS order
-// against the state the guess implies -- the cash chain c_i over the earlier
-// executed orders (the same (((c + X1) - y) - Z) sequence as the serial form)
-// and the canonical trees over the leaves (executed earlier orders: post-order
-// leaves, the rest: pre-order) -- all lanes in parallel.  The checks up to the
-// first order whose outcome contradicts the guess are exact; that order's
-// outcome is taken from its check, later ones are re-guessed, repeat.  Every
-// check that is kept was evaluated on exactly the operands the serial form
-// uses, so the ledger, responses and sums are bit-identical to XRounds; an
-// unrefused batch (the common case) costs one pass instead of S dependent
-// rounds.
-template <int S, bool RQ1, bool ONE>
-__device__ __forceinline__ void broker_spec(Lane<1>& s, const KParams& p, EnvRecs<S>& er,
-                                            double& cash, const double (&uc)[1], double (&tp)[1],
-                                            double (&tu)[1], double (&tc)[1], int (&rk)[1], int ls,
-                                            Sums& after, int& any_mc) {
-  double cu2[1], me2[1], bm3[1], tpr[1], tco[1];
-#ifdef MGN_STAMPS
-  const unsigned long long t_a = __builtin_amdgcn_s_memtime();
-#endif
-  double lf_pre[4], lf_post[4];  // the own leaves and check operands, in registers
-  OwnChk oc[1];
-  order_prep<1, S, false>(s, p, er, uc, ls, cu2, me2, bm3, tpr, tco, lf_pre, lf_post, oc);
-#ifdef MGN_STAMPS
-  const unsigned long long t_b = __builtin_amdgcn_s_memtime();
-#endif
+// The passes of broker_spec: guess, check every order under the guess, fix
+// the first wrong guess, repeat.  PLAIN: the wave's plain form (broker_spec);
+// the same statements on the same operands, with dpp_tree4 over the first two
+// sums and dpp_chain's one-term step.  t_tr / t_ch: the stamp builds' times
+// of the first pass after the trees and after the chain (unused otherwise)
+template <int S, bool RQ1, bool ONE, bool PLAIN>
+__device__ __forceinline__ void spec_passes(const KParams& p, const double (&lf_pre)[4], const double (&lf_post)[4],
+                                            const OwnChk (&oc)[1], int act, uint32_t act_bits, double cash0, int ls,
+                                            int& go, int& mc, int& insuff, double& cend, double (&rootP)[4],
+                                            unsigned long long& t_tr, unsigned long long& t_ch) {
   const OwnChk& own = oc[0];
-  const int act = uc[0] != 0. ? 1 : 0;
-  const uint32_t act_bits = (uint32_t)seg_or<S>(act << ls);
   uint32_t go_bits = act_bits;  // the guess
-  const double cash0 = cash;
-  int go = 0, mc = 0, insuff = 0;
-  double cend = cash0;
-  double rootP[4];  // the sums after the orders the pass took
-#ifdef MGN_STAMPS
-  unsigned long long t_tr = 0, t_ch = 0;
-#endif
   for (int it = 0; it <= S; ++it) {
     // canonical sums before this lane's order: leaves of executed earlier
     // orders after the order, the others before
     double r[4];
-    dpp_tree4<S, ONE>(lf_pre, lf_post, ((go_bits >> ls) & 1) != 0, ls, r, rootP);
+    dpp_tree4<S, ONE, PLAIN ? 2 : 4>(lf_pre, lf_post, ((go_bits >> ls) & 1) != 0, ls, r, rootP);
 #ifdef MGN_STAMPS
     if (it == 0) t_tr = __builtin_amdgcn_s_memtime();
 #endif
@@ -580,7 +562,7 @@ __device__ __forceinline__ void broker_spec(Lane<1>& s, const KParams& p, EnvRec
     double cown1[1];
     {
       const bool g1[1] = {((go_bits >> ls) & 1) != 0};
-      dpp_chain<S, 1>(cash0, oc, g1, ls, cown1, cend);
+      dpp_chain<S, 1, PLAIN>(cash0, oc, g1, ls, cown1, cend);
     }
     const double c_own = cown1[0];
 #ifdef MGN_STAMPS
@@ -606,6 +588,74 @@ __device__ __forceinline__ void broker_spec(Lane<1>& s, const KParams& p, EnvRec
     const uint32_t below = (1u << i0) - 1u;
     go_bits = (go_bits & below) | (go_now & (1u << i0)) | (act_bits & ~(below | (1u << i0)));
   }
+}
+
+// Broker::handleTransaction(units) for a segment of S lanes, one asset per
+// lane, resolved speculatively.  The serial dependency between orders (each
+// risk check sees the cash and portfolio sums the earlier orders left,
+// Broker.cpp:149-155) is only a dependency on which earlier orders executed.
+// Guess that every nonzero order executes; then each lane checks ITS order
+// against the state the guess implies -- the cash chain c_i over the earlier
+// executed orders (the same (((c + X1) - y) - Z) sequence as the serial form)
+// and the canonical trees over the leaves (executed earlier orders: post-order
+// leaves, the rest: pre-order) -- all lanes in parallel.  The checks up to the
+// first order whose outcome contradicts the guess are exact; that order's
+// outcome is taken from its check, later ones are re-guessed, repeat.  Every
+// check that is kept was evaluated on exactly the operands the serial form
+// uses, so the ledger, responses and sums are bit-identical to XRounds; an
+// unrefused batch (the common case) costs one pass instead of S dependent
+// rounds.
+// The plain wave.  With no short position the sh leaves L (meanEntry [L < 0])
+// are +0.0, at required_margin == 1 the borrowed leaves are (amt - amt 1 =
+// +0.0), X1 is -0.0 unless an order closes through a position and Z is +0.0
+// unless borrowed margin is settled: half the trees then sum zeros and two of
+// the chain's three additions are identities.  One test per call, on the
+// bits of the lanes' own operands (they do not change between passes),
+// balloted over the wave -- its active lanes are whole env segments -- asks
+// whether every sh / b leaf, pre and post, and every Z is +0.0 and every X1
+// is -0.0; a -0.0 leaf, a NaN or any other value makes the wave general, and
+// a general wave runs the full passes.  A plain wave's passes are
+// bit-identical to them:
+//  * a sum of +0.0 leaves is +0.0 under every guess (dpp_tree4's NQ = 2
+//    sets those paths and roots without the additions);
+//  * x + (-0.0) == x and x - (+0.0) == x for every x, signed zeros
+//    included, so ((c + X1) - y) - Z == c - y (dpp_chain's PLAIN step; a
+//    skipped order's y is masked to +0.0 in both forms);
+//  * a NaN cash value still passes through c - y in both forms.
+// MGN_ABL_PLAIN_OFF (diagnostic builds) forces the general passes
+template <int S, bool RQ1, bool ONE>
+__device__ __forceinline__ void broker_spec(Lane<1>& s, const KParams& p, EnvRecs<S>& er,
+                                            double& cash, const double (&uc)[1], double (&tp)[1],
+                                            double (&tu)[1], double (&tc)[1], int (&rk)[1], int ls,
+                                            Sums& after, int& any_mc) {
+  double cu2[1], me2[1], bm3[1], tpr[1], tco[1];
+#ifdef MGN_STAMPS
+  const unsigned long long t_a = __builtin_amdgcn_s_memtime();
+#endif
+  double lf_pre[4], lf_post[4];  // the own leaves and check operands, in registers
+  OwnChk oc[1];
+  order_prep<1, S, false>(s, p, er, uc, ls, cu2, me2, bm3, tpr, tco, lf_pre, lf_post, oc);
+#ifdef MGN_STAMPS
+  const unsigned long long t_b = __builtin_amdgcn_s_memtime();
+#endif
+  const int act = uc[0] != 0. ? 1 : 0;
+  const uint32_t act_bits = (uint32_t)seg_or<S>(act << ls);
+  const double cash0 = cash;
+  int go = 0, mc = 0, insuff = 0;
+  double cend = cash0;
+  double rootP[4];  // the sums after the orders the pass took
+  unsigned long long t_tr = 0, t_ch = 0;  // stamp builds
+  // the plain wave's test: any set bit in a lane makes the wave general
+  const long long gen_bits = __double_as_longlong(lf_pre[2]) | __double_as_longlong(lf_post[2]) |
+                             __double_as_longlong(lf_pre[3]) | __double_as_longlong(lf_post[3]) |
+                             __double_as_longlong(oc[0].Z) |
+                             (__double_as_longlong(oc[0].X1) ^ (long long)(1ull << 63));
+  if (!kAblPlainOff && __ballot(gen_bits != 0) == 0)
+    spec_passes<S, RQ1, ONE, true>(p, lf_pre, lf_post, oc, act, act_bits, cash0, ls, go, mc, insuff, cend,
+                                   rootP, t_tr, t_ch);
+  else
+    spec_passes<S, RQ1, ONE, false>(p, lf_pre, lf_post, oc, act, act_bits, cash0, ls, go, mc, insuff, cend,
+                                    rootP, t_tr, t_ch);
   cash = cend;
 #ifdef MGN_STAMPS
   const unsigned long long t_c = __builtin_amdgcn_s_memtime();

@@ -11,6 +11,15 @@ extern "C" int mgn_diag_stamps(unsigned long long* h) {
   unsigned long long z[24] = {};
   return hipMemcpyToSymbol(HIP_SYMBOL(mgn::g_duo_stamps), z, sizeof(z)) != hipSuccess;
 }
+#ifdef MGN_STAMPS
+// the per-role cycles by the iteration's parity (g_trio_par, mgn_diag.h): read and cleared
+extern "C" int mgn_diag_parity(unsigned long long* h) {
+  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(mgn::g_trio_par), 16 * sizeof(unsigned long long)) != hipSuccess)
+    return 1;
+  unsigned long long z[16] = {};
+  return hipMemcpyToSymbol(HIP_SYMBOL(mgn::g_trio_par), z, sizeof(z)) != hipSuccess;
+}
+#endif
 extern "C" int mgn_diag_wall(unsigned long long* h) {
   return hipMemcpyFromSymbol(h, HIP_SYMBOL(mgn::g_duo_wall), 2048 * 32 * sizeof(unsigned long long)) != hipSuccess;
 }

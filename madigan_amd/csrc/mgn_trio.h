@@ -598,7 +598,8 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
     bool shadow = false, tail_it = false, stored = false;
     int jlast = 0;
     __builtin_amdgcn_s_setprio(kPrioG);
-    MGN_ST(unsigned long long T0 = 0, T1 = 0, T2 = 0, acc0 = 0, acc1 = 0; int jn = 0;)
+    MGN_ST(unsigned long long T0 = 0, T1 = 0, T2 = 0, acc0 = 0, acc1 = 0, par[4] = {0, 0, 0, 0},
+           dev[4] = {0, 0, 0, 0}; int jn = 0;)
     int gpend = 0;  // WIN: refill ticks still to come after the reset tick
     RpCurM<M> rp{};  // RP: the current State's tape row, features, dataEnd
     RpNextM<M> rnx{};
@@ -643,6 +644,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
     for (int j = 0;; ++j) {
       const int cur = j & 1, prv = cur ^ 1;
       MGN_T(T0);
+      MGN_ST(MGN_PAR(dev, j, ((ts + (uint64_t)s.dskip) & 1) ? 0 : 1, 1))  // iterations on an even draw index; iterations
       if (threadIdx.x == 0) sh.more[(j + 1) % 3] = 0;
       if (live) {
         if constexpr (TAIL) {
@@ -771,7 +773,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       __syncthreads();
       MGN_T(T2);
       MGN_IT(2 + (j < 40 ? j : 40), 0);
-      MGN_ST(acc0 += T1 - T0; acc1 += T2 - T1; jn = j;)
+      MGN_ST(acc0 += T1 - T0; acc1 += T2 - T1; jn = j; MGN_PAR(par, j, T1 - T0, T2 - T1))
       jlast = j;
       if (trio_exit(j, K, sh.more[j % 3])) break;
     }
@@ -780,6 +782,11 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       atomicAdd(&g_duo_stamps[1], acc1);
       atomicAdd(&g_duo_stamps[8], (unsigned long long)(jn + 1));
       atomicAdd(&g_duo_stamps[10], 1ull);
+      for (int i = 0; i < 4; ++i) atomicAdd(&g_trio_par[i], par[i]);
+      atomicAdd(&g_trio_par[12], dev[0]);
+      atomicAdd(&g_trio_par[13], dev[2]);
+      atomicAdd(&g_trio_par[14], dev[1]);
+      atomicAdd(&g_trio_par[15], dev[3]);
     })
     if constexpr (kAblEpi) return;
     if constexpr (TAIL) {
@@ -849,7 +856,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
     // (stamp builds: the ledger's phases -- prices + pre-order sums, units,
     // the Broker, the records)
     MGN_ST(unsigned long long T0 = 0, T1 = 0, T2 = 0, acc0 = 0, acc1 = 0;
-           unsigned long long Lp1 = 0, Lp2 = 0, Lp3 = 0, lacc[4] = {0, 0, 0, 0};)
+           unsigned long long Lp1 = 0, Lp2 = 0, Lp3 = 0, lacc[4] = {0, 0, 0, 0}, par[4] = {0, 0, 0, 0};)
     for (int j = 0;; ++j) {
       const int cur = j & 1, prv = cur ^ 1;
       MGN_T(T0);
@@ -1074,7 +1081,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       MGN_T(T1);
       __syncthreads();
       MGN_T(T2);
-      MGN_ST(acc0 += T1 - T0; acc1 += T2 - T1;
+      MGN_ST(acc0 += T1 - T0; acc1 += T2 - T1; MGN_PAR(par, j, T1 - T0, T2 - T1)
              if (Lp3 != T0) {  // an iteration that stepped
                lacc[0] += Lp1 - T0;
                lacc[1] += Lp2 - Lp1;
@@ -1093,6 +1100,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       atomicAdd(&g_duo_stamps[3], s_duo_sub[4]);
       atomicAdd(&g_duo_stamps[6], s_duo_sub[7]);
       for (int i = 0; i < 4; ++i) atomicAdd(&g_duo_stamps[20 + i], lacc[i]);
+      for (int i = 0; i < 4; ++i) atomicAdd(&g_trio_par[4 + i], par[i]);
     })
     if constexpr (kAblEpi) return;
     if constexpr (TAIL) {
@@ -1358,7 +1366,8 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
   };
   drain_vmem();
   __builtin_amdgcn_s_setprio(kPrioF);
-  MGN_ST(unsigned long long T0 = 0, T1 = 0, T2 = 0, acc0 = 0, acc1 = 0, Tf1 = 0, Tf2 = 0, facc[3] = {0, 0, 0};)
+  MGN_ST(unsigned long long T0 = 0, T1 = 0, T2 = 0, acc0 = 0, acc1 = 0, Tf1 = 0, Tf2 = 0, facc[3] = {0, 0, 0},
+         par[4] = {0, 0, 0, 0};)
   for (int j = 0;; ++j) {
     const int cur = j & 1, prv = cur ^ 1;
     MGN_T(T0);
@@ -1773,7 +1782,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
     MGN_T(T1);
     __syncthreads();
     MGN_T(T2);
-    MGN_ST(acc0 += T1 - T0; acc1 += T2 - T1;
+    MGN_ST(acc0 += T1 - T0; acc1 += T2 - T1; MGN_PAR(par, j, T1 - T0, T2 - T1)
            if (Tf2) {  // the iterations that evaluated a step: before / in / after the reward's shaping
              facc[0] += Tf1 - T0;
              facc[1] += Tf2 - Tf1;
@@ -1787,6 +1796,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
     atomicAdd(&g_duo_stamps[9], facc[0]);
     atomicAdd(&g_duo_stamps[11], facc[1]);
     atomicAdd(&g_duo_stamps[12], facc[2]);
+    for (int i = 0; i < 4; ++i) atomicAdd(&g_trio_par[8 + i], par[i]);
   })
   if constexpr (kAblEpi) return;
   // the steps still queued (no queue survives a launch): A, B and the episode

@@ -47,6 +47,12 @@ def main():
     torch.cuda.synchronize()
     buf = (C.c_ulonglong * 24)()
     fn(buf)
+    # the same cycles by the iteration's parity (the headline unit's stamp builds)
+    par_fn = getattr(env.lib, "mgn_diag_parity", None) if fn is env.lib.mgn_diag_stamps else None
+    par = (C.c_ulonglong * 16)()
+    if par_fn is not None:
+        par_fn.argtypes = [C.POINTER(C.c_ulonglong)]
+        par_fn(par)
     reps = 10
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -73,6 +79,18 @@ def main():
                       "phases": {k: round(v[i] / it, 1) for k, i in
                                  (("to_reward", 9), ("shaping", 11), ("outputs", 12))}},
            "ledger_passes_per_broker_call": round(v[19] / max(v[18], 1), 3)}
+    if par_fn is not None:
+        par_fn(par)
+        w = list(par)
+        # per role and parity of the iteration j, cycles per iteration of that
+        # parity; even_draw: the share of those iterations in which the
+        # generator began on an even draw index (the pair's whole transform)
+        n = (max(w[14], 1), max(w[15], 1))
+        res["by_iteration_parity"] = {
+            role: {("even_j", "odd_j")[q]: {"work": round(w[4 * r + 2 * q] / n[q], 1),
+                                            "wait": round(w[4 * r + 2 * q + 1] / n[q], 1)} for q in range(2)}
+            for r, role in enumerate(("gen", "ledger", "finish"))}
+        res["by_iteration_parity"]["even_draw_share"] = {"even_j": round(w[12] / n[0], 3), "odd_j": round(w[13] / n[1], 3)}
     print(json.dumps(res))
 
 
