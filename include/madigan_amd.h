@@ -249,7 +249,10 @@ typedef struct {
  * pushed row has 2 columns, the ring stores n_price = 1).  out_stride /
  * out_offset: row stride (0 = n_price) and first column of the gathered price
  * in the caller's buffer, so the rings of a MultiStackerDiscrete
- * (preprocessor.py:202-288) gather side by side into one (N, W, sum) array. */
+ * (preprocessor.py:202-288) gather side by side into one (N, W, sum) array.
+ * n_envs, window and n_price are >= 1 and n_port >= 0: a ring without a price
+ * column is refused with MGN_ERR_LENGTH (no StackerDiscrete class builds one;
+ * the gather writes a row's timestamp along with its first price column). */
 typedef struct {
   int32_t n_envs, n_price, n_port, window, norm_type, transform;
   double *ring;

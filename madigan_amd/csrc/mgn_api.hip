@@ -17,15 +17,14 @@
 
 #include "../../include/madigan_amd.h"
 #include "mgn_aux_kernels.h"
+#include "mgn_gather_plan.h"
 #include "mgn_launch.h"
 #include "mgn_rnorm.h"
 #include "mgn_xbuf.h"
 
 namespace {
 
-// window gather: LDS staging per workgroup (bytes)
-constexpr size_t kGatherLdsTarget = 40 * 1024;
-constexpr size_t kGatherLdsBudget = 64 * 1024;
+using mgn::kGatherLdsBudget;  // window gather: LDS per workgroup (mgn_gather_plan.h)
 // launch-history gather: windows (steps) per workgroup
 constexpr int kHistStepsPerGroup = 16;
 constexpr size_t kHistGroupBytes = 80 * 1024;  // k_hist_gather: output bytes per workgroup to reach
@@ -411,40 +410,26 @@ mgn::RingDesc ring_desc(const mgn_env* e) {
   return r;
 }
 
-// StackerDiscrete.current_data: element-parallel for the element-wise
-// normalisers; column-parallel (two passes over the window per column) for
-// standard_normal
+// StackerDiscrete.current_data: the kernel and its geometry are plan_gather's
+// (mgn_gather_plan.h) -- LDS-staged or element-parallel for the element-wise
+// normalisers, column-parallel (two passes over the window per column) for
+// standard_normal, strided outputs and odd windows
 void launch_gather(const mgn::RingDesc& r, double* price, double* port, uint64_t* ts,
                    hipStream_t stream) {
-  const int C = r.F + r.Pn;
-  if (r.norm == MGN_NORM_STANDARD_NORMAL || r.norm == MGN_NORM_LOG_STANDARD_NORMAL ||
-      r.ostride != r.F || r.ooff != 0) {
-    const int64_t threads = (int64_t)r.N * C;
-    hipLaunchKernelGGL(mgn::k_ring_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                       stream, r, price, port, ts);
-  } else if (r.W % 2 == 0 && (size_t)r.W * (C + 1) * 8 <= kGatherLdsBudget) {
-    // LDS-staged: envs per workgroup so the staged rows fill ~40 KB (4 per CU)
-    const size_t per_env = (size_t)r.W * (C + 1) * 8;
+  const mgn::GatherPlan p = mgn::plan_gather(r.N, r.F, r.Pn, r.W, r.norm, r.ostride, r.ooff);
+  if (p.kernel == mgn::GatherKernel::Lds) {
     mgn::GatherLds g;
-    g.epb = (int)std::min<size_t>(64, std::max<size_t>(1, kGatherLdsTarget / per_env));
-    // small batches (the agent loop's one window per step at a few thousand
-    // envs): no fewer than four workgroups per CU, so the chip fills
-    g.epb = std::max(1, std::min(g.epb, r.N / (4 * 256)));
+    g.epb = p.epb;
     g.inv_f = 1.0f / (float)r.F;
     g.inv_p = 1.0f / (float)r.Pn;
     g.inv_w = 1.0f / (float)r.W;
-    const unsigned blocks = (unsigned)((r.N + g.epb - 1) / g.epb);
-    hipLaunchKernelGGL(mgn::k_ring_gather_lds, dim3(blocks), dim3(256), per_env * g.epb, stream,
-                       r, price, port, ts, g);
-  } else if ((int64_t)r.N * r.W * C < ((int64_t)1 << 31) && r.W % 2 == 0) {
-    const uint32_t pairs = (uint32_t)((int64_t)r.N * r.W * C / 2);
-    const uint32_t per_block = 256 * mgn::GATHER_U;
-    hipLaunchKernelGGL(mgn::k_ring_gather_elem, dim3((pairs + per_block - 1) / per_block), dim3(256),
-                       0, stream, r, price, port, ts, pairs, 1.0 / (double)(r.W * C), 1.0 / (double)C);
-  } else {  // odd window or > 2^31 ring elements: the column-parallel kernel
-    const int64_t threads = (int64_t)r.N * C;
-    hipLaunchKernelGGL(mgn::k_ring_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                       stream, r, price, port, ts);
+    hipLaunchKernelGGL(mgn::k_ring_gather_lds, dim3(p.blocks), dim3(256), p.lds, stream, r, price, port, ts, g);
+  } else if (p.kernel == mgn::GatherKernel::Elem) {
+    const int C = r.F + r.Pn;
+    hipLaunchKernelGGL(mgn::k_ring_gather_elem, dim3(p.blocks), dim3(256), 0, stream, r, price, port, ts,
+                       p.pairs, 1.0 / (double)(r.W * C), 1.0 / (double)C);
+  } else {
+    hipLaunchKernelGGL(mgn::k_ring_gather, dim3(p.blocks), dim3(256), 0, stream, r, price, port, ts);
   }
 }
 
@@ -991,7 +976,8 @@ static mgn::RingDesc ring_from(const mgn_ring* r) {
 
 static int ring_ok(const mgn_ring* r) {
   if (!r || !r->ring || !r->ring_ts || !r->head || !r->len) return fail(nullptr, MGN_ERR_ARG, "null ring buffers");
-  if (r->n_envs < 1 || r->window < 1 || r->n_price < 0 || r->n_port < 0)
+  // n_price >= 1: the gather kernels write the timestamps from price column 0
+  if (r->n_envs < 1 || r->window < 1 || r->n_price < 1 || r->n_port < 0)
     return fail(nullptr, MGN_ERR_LENGTH, "bad ring dimensions");
   if (r->norm_type < 0 || r->norm_type > MGN_NORM_LOG_STANDARD_NORMAL)
     return fail(nullptr, MGN_ERR_CONFIG, "unknown norm_type");

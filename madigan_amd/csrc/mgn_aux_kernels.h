@@ -2,6 +2,7 @@
 // included by exactly one translation unit (mgn_api.hip).
 #pragma once
 
+#include "mgn_gather_plan.h"
 #include "mgn_kernels.h"
 
 namespace mgn {
@@ -154,8 +155,6 @@ __device__ __forceinline__ void divmod_u32(uint32_t n, uint32_t d, double inv, u
   else if (rr >= (int32_t)d) { q += 1; rr -= (int32_t)d; }
   r = (uint32_t)rr;
 }
-
-constexpr int GATHER_U = 4;  // 16-B pairs per lane per pass
 
 __global__ __launch_bounds__(BLOCK) void k_ring_gather_elem(RingDesc r, double* __restrict__ price_out,
                                                             double* __restrict__ port_out,

@@ -118,17 +118,21 @@ class _DeviceRing:
     def stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
     def push(self, price, port, ts):
-        L.check(self.lib.mgn_ring_push(C.byref(self.r), C.c_void_p(price.data_ptr()),
-                                       C.c_void_p(port.data_ptr()), C.c_void_p(ts.data_ptr()),
+        """Rows (N, F) / (N, P) / (N,); a row given as None is pushed as zeros."""
+        L.check(self.lib.mgn_ring_push(C.byref(self.r), self._ptr(price), self._ptr(port), self._ptr(ts),
                                        self.stream()))
 
-    def clear(self):
-        L.check(self.lib.mgn_ring_clear(C.byref(self.r), None, self.stream()))
+    def clear(self, mask=None):
+        """reset_state of the envs with mask[e] != 0 (a uint8 device tensor); None: all."""
+        L.check(self.lib.mgn_ring_clear(C.byref(self.r), self._ptr(mask), self.stream()))
 
     def gather(self, price, port=None, ts=None):
-        ptr = (lambda t: None if t is None else C.c_void_p(t.data_ptr()))
-        L.check(self.lib.mgn_ring_gather(C.byref(self.r), ptr(price), ptr(port), ptr(ts),
+        L.check(self.lib.mgn_ring_gather(C.byref(self.r), self._ptr(price), self._ptr(port), self._ptr(ts),
                                          self.stream()))
 
 
