@@ -42,7 +42,11 @@
  *   mgn_xbuf_*        the uniform experience replay buffer fed from a launch
  *                     (madigan/utils/buffers/replay_buffer.py:23-172 over
  *                     nstep_buffer.py:315-376; offpolicy_q.py:196-207)
- *   mgn_get_views     zero-copy property views (env.cpp:897-913)
+ *   mgn_pbuf_*        its prioritized mode: the sum / min segment trees, the
+ *                     prefix-sum sampling and the priority update
+ *                     (madigan/utils/buffers/prioritized_replay_buffer.py:13-87,
+ *                     segment_tree.py:7-66)
+ *   mgn_get_views    zero-copy property views (env.cpp:897-913)
  *   mgn_last_error    pybind11 exception translation (DataTypes.h:36-46)
  *
  * Threading: a handle is not thread-safe; all work is ordered on the handle's
@@ -354,6 +358,35 @@ typedef struct {
   int64_t *idx;
 } mgn_xbuf_batch;
 
+/* The prioritized mode of an mgn_xbuf (prioritized_replay_buffer.py:13-87):
+ * two segment trees (segment_tree.py:7-66) over the buffer's slots, in
+ * caller-owned device memory.  New symbols only: MGN_ABI_VERSION stays 11.
+ *   tree_size    leaves: the next power of two >= xbuf.size (:32-34)
+ *   tree_sum, tree_min  (2 * tree_size) fp64 heap arrays: node i holds
+ *                values[2i] + values[2i+1] (min(values[2i], values[2i+1])),
+ *                leaf s is node tree_size + s; zeros / +inf when new (:35-36)
+ *   cached_idx   (cached_cap) int64: the slots of the last sampled batch
+ *                (cached_idxs, :62), -1 for a row that drew none
+ *   cached_len   rows cached (host side): set by mgn_pbuf_sample, cleared by
+ *                mgn_pbuf_update; 0 = no batch is cached
+ *   owner        (xbuf.size) int32 scratch of the update, zero between calls
+ *   uniforms     NULL, or (n_batch) fp64 in [0, 1) that replace the Philox
+ *                uniforms of mgn_pbuf_sample (tests inject recorded draws) */
+typedef struct {
+  int64_t tree_size;
+  double *tree_sum, *tree_min;
+  int64_t *cached_idx;
+  int64_t cached_cap, cached_len;
+  int32_t *owner;
+  const double *uniforms;
+} mgn_pbuf;
+
+/* where an added transition's max_pa goes (mgn_pbuf_add) */
+enum {
+  MGN_PBUF_SEAT_NEXT = 0,    /* the reference's: the slot after the one written (:53-55) */
+  MGN_PBUF_SEAT_WRITTEN = 1  /* the slot the transition went to */
+};
+
 typedef struct mgn_env mgn_env;
 
 int mgn_abi_version(void);
@@ -515,6 +548,45 @@ int mgn_xbuf_gather(const mgn_xbuf *xbuf, const int64_t *idx_dev, const mgn_xbuf
  * pops as min(n_shaped, pending at the step), in the scan and in the copy
  * alike, so no slot is counted as filled and left unwritten. */
 int mgn_xbuf_clear(const mgn_xbuf *xbuf, int32_t nstep_only, void *stream);
+/* PrioritizedReplayBuffer._add_to_replay's two tree assignments
+ * (prioritized_replay_buffer.py:52-55, SegmentTree.__setitem__
+ * segment_tree.py:30-40) for every transition of the launch mgn_xbuf_add just
+ * added on the same stream (its plan and plan_base are read): max_pa goes to
+ * the leaves (c0 + off + j) mod size, j < T, of both trees, then their
+ * ancestors are recomputed level by level, each node one ordered left + right
+ * (min(left, right)) -- bit-identical to the T serial assignments, as every
+ * node is a function of its children alone.  c0 is current_idx before the add;
+ * T the add's transitions, counted on the device as the last (step, env)
+ * pair's offset plus its pops, which needs the launch's n_shaped_dev (K,
+ * n_envs) once more; off is 1 for MGN_PBUF_SEAT_NEXT (the reference advances
+ * the cursor first, so the slot after the written one gets the priority) and
+ * 0 for MGN_PBUF_SEAT_WRITTEN.  MGN_ERR_CONFIG before any HIP call: a bad
+ * xbuf, a tree_size that is not the power of two for xbuf.size, null trees or
+ * scratch, a null plan or n_shaped, k_steps outside 1..plan_steps, a NaN
+ * max_pa, an unknown seat. */
+int mgn_pbuf_add(const mgn_xbuf *xbuf, const mgn_pbuf *pbuf, const uint8_t *n_shaped_dev, int32_t k_steps,
+                 double max_pa, int32_t seat, void *stream);
+/* PrioritizedReplayBuffer.sample (prioritized_replay_buffer.py:57-68,
+ * _calc_weight :70-74; SegmentTree.reduce segment_tree.py:14-28,
+ * find_prefixsum_idx :52-61): row i draws u_i in [0, 1) -- (x >> 11) * 2^-53 of
+ * the 64-bit Philox4x32-10 draw keyed by seed at counter (i, call), or
+ * pbuf.uniforms[i] -- and descends the sum tree with u_i * reduce(0, filled);
+ * weights_dev[i] = float32((tree_sum[idx] / min_pa) ** -beta) with min_pa the
+ * min tree's reduce(0, filled) and beta the caller's stepped value.  A row
+ * whose index leaves [0, filled) (rounding, or a zero total) gets idx = -1,
+ * weight 0 and a zero row.  The indices stay in pbuf.cached_idx (cached_len =
+ * n_batch); the batch is mgn_xbuf_gather's of them.  MGN_ERR_CONFIG: a bad
+ * xbuf or pbuf, a null batch or weights, n_batch outside 1..cached_cap. */
+int mgn_pbuf_sample(const mgn_xbuf *xbuf, mgn_pbuf *pbuf, const mgn_xbuf_batch *batch, float *weights_dev,
+                    int64_t n_batch, double beta, uint64_t seed, uint64_t call, void *stream);
+/* PrioritizedReplayBuffer.update_priority's loop (prioritized_replay_buffer.py
+ * :80-83): pa_dev (n_batch) fp64 goes to the cached slots' leaves of both
+ * trees, the last row of a duplicated slot winning as in the serial loop (an
+ * integer atomicMax of the row number per slot; no float atomics), and the
+ * touched paths are recomputed level by level.  Rows of idx = -1 are skipped.
+ * Clears the cache.  MGN_ERR_CONFIG: a bad xbuf or pbuf, a null pa_dev, no
+ * cached batch, n_batch != cached_len. */
+int mgn_pbuf_update(const mgn_xbuf *xbuf, mgn_pbuf *pbuf, const double *pa_dev, int64_t n_batch, void *stream);
 /* Lane layout of the step kernels: assets held per lane (1, 2, 4, 8; 0 =
  * automatic, the default).  Results are bit-identical for every layout (the
  * canonical reduction tree does not depend on it); only speed changes. */

@@ -13,12 +13,14 @@ from .env import (Asset, BatchedEnv, BrokerResponse, DataSourceTick, Env, EnvInf
                   get_env_info, make_batched_env, make_env)
 from .hdf import HDFSourceSingle, write_hdf
 from .replay_buffer import DeviceReplayBuffer
+from .prioritized_replay_buffer import DevicePrioritizedReplayBuffer, make_buffer_from_config
 from .preprocessor import (MultiStackerDiscrete, PreProcessor, StackerDiscrete, StackerDiscretePairs,
                            StackerDiscreteReturns, make_preprocessor)
 
-__all__ = ["Asset", "BatchedEnv", "BrokerResponse", "ConfigError", "DataSourceTick", "DeviceReplayBuffer", "Env",
+__all__ = ["Asset", "BatchedEnv", "BrokerResponse", "ConfigError", "DataSourceTick", "DevicePrioritizedReplayBuffer",
+           "DeviceReplayBuffer", "Env",
            "EnvInfo", "HDFSourceSingle", "PreProcessor", "RiskInfo", "SourceSpec",
-           "StackerDiscrete", "State", "get_env_info", "make_batched_env", "make_env",
+           "StackerDiscrete", "State", "get_env_info", "make_batched_env", "make_buffer_from_config", "make_env",
            "make_preprocessor", "MultiStackerDiscrete", "StackerDiscretePairs",
            "StackerDiscreteReturns", "replay_spec", "spec_from_config", "write_hdf"]
 

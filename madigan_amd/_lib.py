@@ -123,6 +123,14 @@ class XBufBatch(C.Structure):  # mgn_xbuf_batch
     _fields_ = [(n, C.c_void_p) for n in XBUF_BATCH_FIELDS]
 
 
+class PBuf(C.Structure):  # mgn_pbuf
+    _fields_ = [("tree_size", C.c_int64), ("tree_sum", C.c_void_p), ("tree_min", C.c_void_p),
+                ("cached_idx", C.c_void_p), ("cached_cap", C.c_int64), ("cached_len", C.c_int64),
+                ("owner", C.c_void_p), ("uniforms", C.c_void_p)]
+
+
+PBUF_SEAT_NEXT, PBUF_SEAT_WRITTEN = 0, 1
+
 SYMBOLS = {
     # name: (restype, argtypes)
     "mgn_abi_version": (C.c_int, []),
@@ -167,6 +175,11 @@ SYMBOLS = {
                                   C.c_void_p]),
     "mgn_xbuf_gather": (C.c_int, [C.POINTER(XBuf), C.c_void_p, C.POINTER(XBufBatch), C.c_int64, C.c_void_p]),
     "mgn_xbuf_clear": (C.c_int, [C.POINTER(XBuf), C.c_int32, C.c_void_p]),
+    "mgn_pbuf_add": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.c_void_p, C.c_int32, C.c_double, C.c_int32,
+                               C.c_void_p]),
+    "mgn_pbuf_sample": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.POINTER(XBufBatch), C.c_void_p, C.c_int64,
+                                  C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "mgn_pbuf_update": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.c_void_p, C.c_int64, C.c_void_p]),
     "mgn_set_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "mgn_get_layout": (C.c_int, [C.c_void_p]),
     "mgn_set_schedule": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -20,6 +20,7 @@
 #include "mgn_gather_plan.h"
 #include "mgn_launch.h"
 #include "mgn_rnorm.h"
+#include "mgn_pbuf.h"
 #include "mgn_xbuf.h"
 
 namespace {
@@ -1124,6 +1125,67 @@ int mgn_xbuf_clear(const mgn_xbuf* x, int32_t nstep_only, void* stream) {
   int rc = xbuf_ok(x);
   if (rc != MGN_OK) return rc;
   return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_clear(*x, nstep_only, stream), "mgn_xbuf_clear");
+}
+
+static int pbuf_ok(const mgn_xbuf* x, const mgn_pbuf* p) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!p) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer");
+  if (p->tree_size != mgn::pb_tree_size(x->size))
+    return fail(nullptr, MGN_ERR_CONFIG, "prioritized buffer: tree_size must be the next power of two >= size");
+  if (!p->tree_sum || !p->tree_min) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer trees");
+  if (!p->cached_idx || !p->owner) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer index cache or scratch");
+  if (p->cached_cap < 1 || p->cached_cap >= ((int64_t)1 << 31) || p->cached_len < 0 || p->cached_len > p->cached_cap)
+    return fail(nullptr, MGN_ERR_CONFIG, "prioritized buffer: cached_cap must be 1..2^31-1 and cached_len within it");
+  return MGN_OK;
+}
+
+// prioritized_replay_buffer.py:52-55 (segment_tree.py:30-40)
+int mgn_pbuf_add(const mgn_xbuf* x, const mgn_pbuf* p, const uint8_t* n_shaped_dev, int32_t k_steps, double max_pa,
+                 int32_t seat, void* stream) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!n_shaped_dev || !x->plan || !x->plan_base)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: null n_shaped or plan arrays");
+  if (k_steps < 1 || k_steps > x->plan_steps)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: k_steps must be 1..plan_steps");
+  if (max_pa != max_pa) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: max_pa is NaN");
+  if (seat != MGN_PBUF_SEAT_NEXT && seat != MGN_PBUF_SEAT_WRITTEN)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: seat must be MGN_PBUF_SEAT_NEXT or MGN_PBUF_SEAT_WRITTEN");
+  return check_hip(nullptr,
+                   (hipError_t)mgn::pbuf_launch_add(*x, *p, n_shaped_dev, k_steps, max_pa,
+                                                    seat == MGN_PBUF_SEAT_NEXT ? 1 : 0, stream),
+                   "mgn_pbuf_add");
+}
+
+// prioritized_replay_buffer.py:57-74 (segment_tree.py:14-28, :52-61)
+int mgn_pbuf_sample(const mgn_xbuf* x, mgn_pbuf* p, const mgn_xbuf_batch* batch, float* weights_dev, int64_t n_batch,
+                    double beta, uint64_t seed, uint64_t call, void* stream) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!batch || !weights_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_sample: null batch or weights");
+  if (n_batch < 1 || n_batch > p->cached_cap)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_sample: n_batch must be 1..cached_cap");
+  rc = check_hip(nullptr, (hipError_t)mgn::pbuf_launch_draw(*x, *p, weights_dev, n_batch, beta, seed, call, stream),
+                 "mgn_pbuf_sample");
+  if (rc != MGN_OK) return rc;
+  p->cached_len = n_batch;
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather(*x, p->cached_idx, *batch, n_batch, 0, 0, stream),
+                   "mgn_pbuf_sample");
+}
+
+// prioritized_replay_buffer.py:76-83
+int mgn_pbuf_update(const mgn_xbuf* x, mgn_pbuf* p, const double* pa_dev, int64_t n_batch, void* stream) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!pa_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: null priorities");
+  if (p->cached_len < 1)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: no cached batch (sample another batch before updating priorities)");
+  if (n_batch < 1 || n_batch != p->cached_len)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: n_batch differs from the cached batch");
+  rc = check_hip(nullptr, (hipError_t)mgn::pbuf_launch_update(*x, *p, pa_dev, n_batch, stream), "mgn_pbuf_update");
+  if (rc == MGN_OK) p->cached_len = 0;
+  return rc;
 }
 
 int mgn_set_layout(mgn_env* e, int32_t assets_per_lane) {

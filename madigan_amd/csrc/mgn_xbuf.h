@@ -115,8 +115,9 @@ MGN_XB_HD void xb_advance(int64_t& current_idx, int64_t& filled, int64_t total, 
 // sample call counter, slot XB_PHILOX_SLOT of asset 0; the key is the seed.
 constexpr uint32_t XB_PHILOX_SLOT = 0x5B;
 
-MGN_XB_HD uint64_t xb_draw64(uint64_t seed, uint64_t call, uint64_t draw) {
-  uint32_t c0 = (uint32_t)draw, c1 = (uint32_t)call, c2 = XB_PHILOX_SLOT << 16,
+// (the slot tag is a parameter for the prioritized sampler's own stream, mgn_pbuf.h)
+MGN_XB_HD uint64_t xb_draw64_slot(uint64_t seed, uint64_t call, uint64_t draw, uint32_t slot) {
+  uint32_t c0 = (uint32_t)draw, c1 = (uint32_t)call, c2 = slot << 16,
            c3 = (uint32_t)(draw >> 32) ^ (uint32_t)(call >> 32);
   uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   for (int r = 0; r < 10; ++r) {
@@ -132,6 +133,10 @@ MGN_XB_HD uint64_t xb_draw64(uint64_t seed, uint64_t call, uint64_t draw) {
     k1 += 0xBB67AE85u;
   }
   return ((uint64_t)c1 << 32) | c0;
+}
+
+MGN_XB_HD uint64_t xb_draw64(uint64_t seed, uint64_t call, uint64_t draw) {
+  return xb_draw64_slot(seed, call, draw, XB_PHILOX_SLOT);
 }
 
 // floor(x * m / 2^64) from 32-bit halves (no 128-bit type needed)

@@ -23,8 +23,9 @@ right after the clears).  ``clear_nstep()`` (and ``clear()``) go with
 ``env.clear_nstep()``, and the other way round: ``buf.clear_nstep(env)`` does
 both.
 
-There is no CPU fallback.  Out of scope: the prioritized and the recurrent
-buffer, windows under the per-window normalisers (standard_normal,
+There is no CPU fallback.  The prioritized buffer is
+``prioritized_replay_buffer.DevicePrioritizedReplayBuffer``, a subclass.  Out
+of scope: the recurrent buffer, windows under the per-window normalisers (standard_normal,
 lookback...), continuous-action launches and replay-tape sources (their
 ``data_end`` steps, which the reference's loop skips, are not handled).
 """
