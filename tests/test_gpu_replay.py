@@ -38,10 +38,14 @@ def hdf_config(path, cache, start=None, end=None):
 @pytest.mark.parametrize("A,F,cache,stride,window,norm,sched", [
     (3, 5, 37, 7, 8, "lookback", "auto"), (1, 2, 300, 0, 0, None, "auto"),
     (8, 8, 64, 11, 16, "log", "auto"), (8, 8, 64, 11, 16, "log", "single"),
-    (16, 3, 25, 5, 4, "standard_normal", "auto"), (16, 16, 25, 5, 0, None, "auto")])
+    (16, 3, 25, 5, 4, "standard_normal", "auto"), (16, 16, 25, 5, 0, None, "auto"),
+    # more than 16 assets (units a32 / a64): more features than assets, and fewer
+    (33, 40, 37, 7, 4, "lookback", "auto"), (33, 40, 37, 7, 0, None, "auto"),
+    (64, 3, 25, 5, 4, "log", "auto"), (64, 3, 25, 5, 0, None, "auto")])
 def test_replay_rollout_bitwise(gpu, tmp_path, A, F, cache, stride, window, norm, sched):
-    """Both step schedules: "auto" runs the two-role kernel for A >= 2 (tape
-    rows prefetched by the generator lanes), "single" forces k_step."""
+    """Both step schedules: "auto" runs the two-role kernel for 2 <= A <= 16
+    (tape rows prefetched by the generator lanes) and k_step above 16 assets,
+    "single" forces k_step."""
     from madigan_amd import BatchedEnv
     from madigan_amd import _lib as L
     from madigan_amd.config import spec_from_config
@@ -60,7 +64,7 @@ def test_replay_rollout_bitwise(gpu, tmp_path, A, F, cache, stride, window, norm
     if sched == "single":
         L.check(g.lib.mgn_set_schedule(g.h, L.SCHED_SINGLE), g.h)
     else:
-        assert g.lib.mgn_get_schedule(g.h) == (L.SCHED_DUO if A >= 2 else L.SCHED_SINGLE)
+        assert g.lib.mgn_get_schedule(g.h) == (L.SCHED_DUO if 2 <= A <= 16 else L.SCHED_SINGLE)
     first, second, _, _ = O.hdf_bounds(ts, start, end)
     okw = dict(kw, n_envs=N, n_feats=F, auto_reset=1)
     orc = O.OracleBatch(okw, [(O.SRC_REPLAY, [])] * A)

@@ -169,6 +169,11 @@ ROWS = [
     ("32 assets, 65536 envs", "A=32 N=65536", single("a32", (64, 256, 0), 8, 4)),
     ("64 assets", "A=64", single("a64", (16, 256, 0), 4, 16)),
     ("64 assets, 65536 envs", "A=64 N=65536 rq1=0", single("a64", (32, 256, 0), 8, 8, rq1=0)),
+    ("17 assets: the 32-slot unit", "A=17", single("a32", (16, 256, 0), 2, 16)),
+    ("33 assets: the 64-slot unit", "A=33 rq1=0 nstep=20", single("a64", (16, 256, 0), 4, 16, rq1=0, nst=1)),
+    ("64 assets, one slot per lane asked for: raised to min_m", "A=64 m=1", single("a64", (16, 256, 0), 4, 16)),
+    ("17 assets x 40 envs, 8 slots per lane by hand", "A=17 N=40 m=8 aux=1", single("a32", (64, 256, 0), 8, 4)),
+    ("64 assets x 40 envs, per-asset n-step", "A=64 N=40 D=64 nstep=5 aux=1", single("a64", (16, 256, 0), 4, 16, nst=1)),
     ("aux on (multi-component sources)", "aux=1", single("a8", (32, 256, 0), 1, 8)),
     ("assets per lane set by hand", "gkind=TrendOU m=2", single("a8", (64, 256, 0), 2, 4)),
     # ---- forced schedules, on an eligible and an ineligible handle each
