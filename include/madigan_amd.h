@@ -36,6 +36,9 @@
  *   mgn_window_hist   of the agent loop (madigan/modelling/algorithm/
  *   mgn_rollout_window offpolicy_q.py:143, 193-194): K steps in one launch,
  *                     then every step's window
+ *   mgn_rollout_weights  K steps of the actor-critic agents: portfolio weights
+ *   mgn_weights_to_units to units in the launch (madigan/modelling/algorithm/
+ *                     ddpg.py:183-208, :396-421; offpolicy_ac.py:86-137)
  *   mgn_rnorm_*       the streaming reward normalisers and their reset
  *                     (madigan/environments/reward_normalization.pyx:61-272;
  *                     offpolicy_q.py:413-414, :428-429)
@@ -358,6 +361,20 @@ typedef struct {
   int64_t *idx;
 } mgn_xbuf_batch;
 
+/* The float actions of a replay buffer fed by portfolio-weight launches
+ * (mgn_rollout_weights_hist): mgn_xbuf and mgn_xbuf_batch keep their layouts,
+ * and the buffer's int64 action store is then unused.  New symbols only:
+ * MGN_ABI_VERSION stays 11.
+ *   action   (size, A+1)  SARSD.action: the weights row of the pop's origin step
+ *   carry    (n_envs, max(n-1, 1), A+1)  the last n - 1 steps' rows, for
+ *            entries pending at a launch's end (as mgn_xbuf.carry_act)
+ *   f32      0: both stored as float64; 1: rounded once to nearest float32 */
+typedef struct {
+  void *action;
+  void *carry;
+  int32_t f32, pad_;
+} mgn_xbuf_wact;
+
 /* The prioritized mode of an mgn_xbuf (prioritized_replay_buffer.py:13-87):
  * two segment trees (segment_tree.py:7-66) over the buffer's slots, in
  * caller-owned device memory.  New symbols only: MGN_ABI_VERSION stays 11.
@@ -409,6 +426,28 @@ int mgn_step(mgn_env *env, int32_t kind, const double *units_dev, const int32_t 
 int mgn_rollout(mgn_env *env, const int8_t *actions_dev, int32_t k_steps, const mgn_traj *out);
 /* k_steps fused Env::step(units); units_dev (K,N,A) fp64 */
 int mgn_rollout_units(mgn_env *env, const double *units_dev, int32_t k_steps, const mgn_traj *out);
+/* k_steps fused steps of the actor-critic agents (DDPG.action_to_transaction,
+ * ddpg.py:183-208; DDPGDiscretized :396-421): weights_dev (K,N,A+1) fp64
+ * portfolio weights, cash first.  Before step k's Broker pass, per env, on the
+ * state the step starts from (after an in-launch reset: no position, equity =
+ * init_cash), all in fp64 with correctly rounded quotients:
+ *   sumw = w[0] + canonical tree sum of w[1..A]
+ *   d_i = sumw == 0 ? w_i : w_i / sumw;  c_i = (ledger_i * price_i) / equity
+ *   x_i = d_i - c_i, dropped to 0 where transaction_thresh > 0 and |x_i| below it
+ *   units_i = (x_i * equity) / price_i
+ * and the step is mgn_rollout_units' from there (tunits reports the units).
+ * Always runs the single-role kernel at the handle's layout, whatever the
+ * schedule.  Errors as mgn_rollout_units; MGN_ERR_CONFIG for a NaN or negative
+ * transaction_thresh.  mgn_rollout_weights_hist also keeps the launch history,
+ * as mgn_rollout_hist does (and fails as it does).  mgn_weights_to_units writes
+ * the units the next step would order from weights_dev (N,A+1) to units_dev
+ * (N,A) and changes no state. */
+int mgn_rollout_weights(mgn_env *env, const double *weights_dev, int32_t k_steps, double transaction_thresh,
+                        const mgn_traj *out);
+int mgn_rollout_weights_hist(mgn_env *env, const double *weights_dev, int32_t k_steps,
+                             double transaction_thresh, const mgn_traj *out);
+int mgn_weights_to_units(mgn_env *env, const double *weights_dev, double transaction_thresh,
+                         double *units_dev);
 /* prices (N,A) consumed by the next getData of MGN_SRC_EXTERNAL assets */
 int mgn_set_prices(mgn_env *env, const double *prices_dev);
 /* Env::setDataSource (Env.h:174-179; PyDataSource.h:9-15): swap the price
@@ -548,6 +587,21 @@ int mgn_xbuf_gather(const mgn_xbuf *xbuf, const int64_t *idx_dev, const mgn_xbuf
  * pops as min(n_shaped, pending at the step), in the scan and in the copy
  * alike, so no slot is counted as filled and left unwritten. */
 int mgn_xbuf_clear(const mgn_xbuf *xbuf, int32_t nstep_only, void *stream);
+/* The float actions of the launch mgn_xbuf_add just added on the same stream
+ * (its plan and plan_base are read, as mgn_pbuf_add reads them): weights_dev
+ * (K, n_envs, A+1) fp64, the launch's input; every transition's slot gets the
+ * row of its origin step (a carried row for an entry of an earlier launch),
+ * in the same step, env, pop order, and the carry keeps the last n - 1 rows.
+ * mgn_xbuf_add itself is given int8 actions it may read (zeros).
+ * MGN_ERR_CONFIG before any HIP call: a bad xbuf, a null wact store, carry,
+ * weights, n_shaped or plan, k_steps outside 1..plan_steps. */
+int mgn_xbuf_add_wact(const mgn_xbuf *xbuf, const mgn_xbuf_wact *wact, const double *weights_dev,
+                      const uint8_t *n_shaped_dev, int32_t k_steps, void *stream);
+/* action_out (n_batch, A+1), in the store's type: the rows of the slots
+ * idx_dev (n_batch) int64, as a sample / gather / prioritized draw just wrote
+ * them to mgn_xbuf_batch.idx; zeros for an index outside [0, filled) */
+int mgn_xbuf_gather_wact(const mgn_xbuf *xbuf, const mgn_xbuf_wact *wact, const int64_t *idx_dev,
+                         void *action_out, int64_t n_batch, void *stream);
 /* PrioritizedReplayBuffer._add_to_replay's two tree assignments
  * (prioritized_replay_buffer.py:52-55, SegmentTree.__setitem__
  * segment_tree.py:30-40) for every transition of the launch mgn_xbuf_add just

@@ -123,6 +123,10 @@ class XBufBatch(C.Structure):  # mgn_xbuf_batch
     _fields_ = [(n, C.c_void_p) for n in XBUF_BATCH_FIELDS]
 
 
+class XBufWact(C.Structure):  # mgn_xbuf_wact
+    _fields_ = [("action", C.c_void_p), ("carry", C.c_void_p), ("f32", C.c_int32), ("pad_", C.c_int32)]
+
+
 class PBuf(C.Structure):  # mgn_pbuf
     _fields_ = [("tree_size", C.c_int64), ("tree_sum", C.c_void_p), ("tree_min", C.c_void_p),
                 ("cached_idx", C.c_void_p), ("cached_cap", C.c_int64), ("cached_len", C.c_int64),
@@ -144,6 +148,9 @@ SYMBOLS = {
     "mgn_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgn_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Traj)]),
     "mgn_rollout_units": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Traj)]),
+    "mgn_rollout_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(Traj)]),
+    "mgn_rollout_weights_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(Traj)]),
+    "mgn_weights_to_units": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "mgn_set_prices": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mgn_set_sources": (C.c_int, [C.c_void_p, C.POINTER(AssetSource), C.c_void_p]),
     "mgn_stats_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -175,6 +182,10 @@ SYMBOLS = {
                                   C.c_void_p]),
     "mgn_xbuf_gather": (C.c_int, [C.POINTER(XBuf), C.c_void_p, C.POINTER(XBufBatch), C.c_int64, C.c_void_p]),
     "mgn_xbuf_clear": (C.c_int, [C.POINTER(XBuf), C.c_int32, C.c_void_p]),
+    "mgn_xbuf_add_wact": (C.c_int, [C.POINTER(XBuf), C.POINTER(XBufWact), C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p]),
+    "mgn_xbuf_gather_wact": (C.c_int, [C.POINTER(XBuf), C.POINTER(XBufWact), C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
     "mgn_pbuf_add": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.c_void_p, C.c_int32, C.c_double, C.c_int32,
                                C.c_void_p]),
     "mgn_pbuf_sample": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.POINTER(XBufBatch), C.c_void_p, C.c_int64,

@@ -4,7 +4,8 @@
 
 Translation units: mgn_api.hip (C ABI, window/action kernels) plus one
 mgn_launch_a<APAD>.hip per padded asset count with that APAD's (M, S)
-instantiations of the step kernels; they compile in parallel and link into
+instantiations of the step kernels (and mgn_launch_a<APAD>w.hip with its
+portfolio-weight instantiations); they compile in parallel and link into
 one shared library.  Strict IEEE binary64 on the device: -ffp-contract=off, no
 fast-math, so the kernels evaluate the same sequence of correctly rounded
 operations as the oracle.
@@ -47,6 +48,16 @@ UNIT_FLAGS = {f"mgn_launch_{u}.hip": _NO_LICM
               for u in ("a1", "a1t", "a1tnst", "a2", "a2nst", "a4", "a4nst", "a8", "a8k1", "a8k1w", "a8nst", "a16", "a16m2",
                         "a16nst",
                         "a32", "a64")}
+# the portfolio-weight units (k_step's IN_WEIGHTS instantiations, one unit per
+# padded asset count beside mgn_launch_a<APAD>.hip) are built like those.  A
+# table of their own: tests/test_build.py derives one case per name of
+# UNIT_FLAGS with the pattern of the units above; theirs are in
+# tests/test_weight_cases_cpu.py
+WTS_UNIT_FLAGS = {f"mgn_launch_a{a}w.hip": _NO_LICM for a in (1, 2, 4, 8, 16, 32, 64)}
+
+
+def unit_flags(name: str) -> list:
+    return UNIT_FLAGS.get(name) or WTS_UNIT_FLAGS.get(name, [])
 
 
 def hipcc() -> str:
@@ -167,7 +178,7 @@ def _flags_key() -> str:
     digest of every source and header (content, not mtime: an edit made while
     a build was compiling must not look built)."""
     import hashlib
-    units = {os.path.basename(s): UNIT_FLAGS.get(os.path.basename(s), []) for s in sources()}
+    units = {os.path.basename(s): unit_flags(os.path.basename(s)) for s in sources()}
     h = hashlib.sha256()
     for d in sorted(deps()):
         with open(d, "rb") as f:
@@ -211,7 +222,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
 
     def compile_one(src):
         obj = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
-        cmd = [cc, *FLAGS, *UNIT_FLAGS.get(os.path.basename(src), []),
+        cmd = [cc, *FLAGS, *unit_flags(os.path.basename(src)),
                "-Rpass-analysis=kernel-resource-usage", "-c", "-o", obj, src]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

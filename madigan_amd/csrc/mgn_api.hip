@@ -378,10 +378,12 @@ void (*const kVal[7])(int, const mgn::ValArgs&) = {mgn::launch_val_a1, mgn::laun
 // launches the step kernel mgn_select.h chooses.  A choice no unit serves, or
 // a dynamic LDS size the device refuses, is an error (the caller's check_hip
 // reports it), never a step that silently did nothing
+// (IN_WEIGHTS: units holds the weights (K, N, A + 1), wthresh their threshold)
 hipError_t launch_step(const mgn_env* e, const mgn_traj& out, int in_kind, const double* units,
                        const int32_t* aidx, const int8_t* act, int K, hipEvent_t ev0 = nullptr,
-                       hipEvent_t ev1 = nullptr) {
-  const mgn::StepArgs a{kparams(e), out, in_kind, units, aidx, act, K, e->stream, ev0, ev1};
+                       hipEvent_t ev1 = nullptr, double wthresh = 0.) {
+  mgn::StepArgs a{kparams(e), out, in_kind, units, aidx, act, K, e->stream, ev0, ev1};
+  if (in_kind == mgn::IN_WEIGHTS) a.p.wthresh = wthresh;
   int gkind = -1;
 #if !(defined(MGN_DIAG) && defined(MGN_NO_GK))  // diagnostic A/B builds: the generic generator role everywhere
   gkind = e->kinds[0];
@@ -401,6 +403,14 @@ void launch_val(const mgn_env* e, double* out) {
   mgn::ValArgs a{kparams(e), out, e->stream};
   launch(kVal, e, a);
 }
+void (*const kWtu[7])(int, const mgn::WtuArgs&) = {mgn::launch_wtu_a1, mgn::launch_wtu_a2, mgn::launch_wtu_a4, mgn::launch_wtu_a8, mgn::launch_wtu_a16, mgn::launch_wtu_a32, mgn::launch_wtu_a64};
+void launch_wtu(const mgn_env* e, const double* weights, double thresh, double* out) {
+  mgn::WtuArgs a{kparams(e), weights, out, e->stream};
+  a.p.wthresh = thresh;
+  launch(kWtu, e, a);
+}
+// a transaction threshold is a number >= 0 (0: plain DDPG)
+bool thresh_ok(double t) { return t >= 0.; }
 
 mgn::RingDesc ring_desc(const mgn_env* e) {
   mgn::RingDesc r;
@@ -646,6 +656,27 @@ int mgn_rollout_units(mgn_env* e, const double* units_dev, int32_t k_steps, cons
   return check_step(e, lst, "mgn_rollout_units");
 }
 
+int mgn_rollout_weights(mgn_env* e, const double* weights_dev, int32_t k_steps, double transaction_thresh,
+                        const mgn_traj* out) {
+  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
+  if (!weights_dev || !out) return fail(e, MGN_ERR_ARG, "null weights/out");
+  if (k_steps < 1) return fail(e, MGN_ERR_LENGTH, "k_steps must be >= 1");
+  if (!thresh_ok(transaction_thresh)) return fail(e, MGN_ERR_CONFIG, "transaction_thresh must be a number >= 0");
+  if (need_tape(e) != MGN_OK) return MGN_ERR_CONFIG;
+  const hipError_t lst = launch_step(e, *out, mgn::IN_WEIGHTS, weights_dev, nullptr, nullptr, (int)k_steps, nullptr,
+                                     nullptr, transaction_thresh);
+  return check_step(e, lst, "mgn_rollout_weights");
+}
+
+int mgn_weights_to_units(mgn_env* e, const double* weights_dev, double transaction_thresh, double* units_dev) {
+  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
+  if (!weights_dev || !units_dev) return fail(e, MGN_ERR_ARG, "null weights/units");
+  if (!thresh_ok(transaction_thresh)) return fail(e, MGN_ERR_CONFIG, "transaction_thresh must be a number >= 0");
+  if (need_tape(e) != MGN_OK) return MGN_ERR_CONFIG;
+  launch_wtu(e, weights_dev, transaction_thresh, units_dev);
+  return check_hip(e, hipGetLastError(), "mgn_weights_to_units");
+}
+
 int mgn_set_prices(mgn_env* e, const double* prices_dev) {
   if (!e || !prices_dev) return fail(e, MGN_ERR_ARG, "null handle/prices");
   return check_hip(e, hipMemcpyAsync(e->v.ext_prices, prices_dev, sizeof(double) * e->N * e->A,
@@ -784,9 +815,10 @@ int mgn_get_timing(mgn_env* e, double* out4) {
   return MGN_OK;
 }
 
-int mgn_rollout_hist(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, const mgn_traj* out) {
-  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
-  if (!actions_dev || !out) return fail(e, MGN_ERR_ARG, "null actions/out");
+// a launch that keeps its history: discrete atoms (actions_dev), or portfolio
+// weights (weights_dev, IN_WEIGHTS)
+static int rollout_hist(mgn_env* e, int in_kind, const int8_t* actions_dev, const double* weights_dev,
+                        double wthresh, int32_t k_steps, const mgn_traj* out, const char* what) {
   if (k_steps < 1) return fail(e, MGN_ERR_LENGTH, "k_steps must be >= 1");
   if (e->W == 0) return fail(e, MGN_ERR_CONFIG, "handle has no window (window_length = 0)");
   if (k_steps > mgn::HIST_KMAX) return fail(e, MGN_ERR_LENGTH, "the launch history holds at most 64 steps");
@@ -822,12 +854,28 @@ int mgn_rollout_hist(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, con
                      hb.ts, (int)rows);
   time_mark(e, e->t_step, e->t_step_n, e->stream);
   e->hist_on = true;
-  const hipError_t lst = launch_step(e, *out, mgn::IN_DISCRETE, nullptr, nullptr, actions_dev, (int)k_steps);
+  const hipError_t lst = launch_step(e, *out, in_kind, weights_dev, nullptr, actions_dev, (int)k_steps, nullptr,
+                                     nullptr, wthresh);
   e->hist_on = false;
   time_mark(e, e->t_step, e->t_step_n, e->stream);
   hb.k = k_steps;
   if (e->wstream) (void)hipEventRecord(hb.ready, e->stream);
-  return check_step(e, lst, "mgn_rollout_hist");
+  return check_step(e, lst, what);
+}
+
+int mgn_rollout_hist(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, const mgn_traj* out) {
+  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
+  if (!actions_dev || !out) return fail(e, MGN_ERR_ARG, "null actions/out");
+  return rollout_hist(e, mgn::IN_DISCRETE, actions_dev, nullptr, 0., k_steps, out, "mgn_rollout_hist");
+}
+
+int mgn_rollout_weights_hist(mgn_env* e, const double* weights_dev, int32_t k_steps, double transaction_thresh,
+                             const mgn_traj* out) {
+  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
+  if (!weights_dev || !out) return fail(e, MGN_ERR_ARG, "null weights/out");
+  if (!thresh_ok(transaction_thresh)) return fail(e, MGN_ERR_CONFIG, "transaction_thresh must be a number >= 0");
+  return rollout_hist(e, mgn::IN_WEIGHTS, nullptr, weights_dev, transaction_thresh, k_steps, out,
+                      "mgn_rollout_weights_hist");
 }
 
 int mgn_window_hist(mgn_env* e, double* price_dev, double* port_dev, uint64_t* ts_dev) {
@@ -1125,6 +1173,38 @@ int mgn_xbuf_clear(const mgn_xbuf* x, int32_t nstep_only, void* stream) {
   int rc = xbuf_ok(x);
   if (rc != MGN_OK) return rc;
   return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_clear(*x, nstep_only, stream), "mgn_xbuf_clear");
+}
+
+static int wact_ok(const mgn_xbuf* x, const mgn_xbuf_wact* w) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!w || !w->action || !w->carry) return fail(nullptr, MGN_ERR_CONFIG, "null weight-action store or carry");
+  return MGN_OK;
+}
+
+int mgn_xbuf_add_wact(const mgn_xbuf* x, const mgn_xbuf_wact* w, const double* weights_dev,
+                      const uint8_t* n_shaped_dev, int32_t k_steps, void* stream) {
+  int rc = wact_ok(x, w);
+  if (rc != MGN_OK) return rc;
+  if (!weights_dev || !n_shaped_dev || !x->plan || !x->plan_base)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: null weights, n_shaped or plan arrays");
+  if (k_steps < 1 || k_steps > x->plan_steps)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: k_steps must be 1..plan_steps");
+  if ((int64_t)k_steps * x->n_envs >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: launch exceeds 2^31 (step, env) pairs");
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_add_wact(*x, *w, weights_dev, n_shaped_dev, k_steps, stream),
+                   "mgn_xbuf_add_wact");
+}
+
+int mgn_xbuf_gather_wact(const mgn_xbuf* x, const mgn_xbuf_wact* w, const int64_t* idx_dev, void* action_out,
+                         int64_t n_batch, void* stream) {
+  int rc = wact_ok(x, w);
+  if (rc != MGN_OK) return rc;
+  if (!idx_dev || !action_out) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather_wact: null indices or output");
+  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather_wact: n_batch must be 1..2^31-1");
+  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather_wact(*x, *w, idx_dev, action_out, n_batch, stream),
+                   "mgn_xbuf_gather_wact");
 }
 
 static int pbuf_ok(const mgn_xbuf* x, const mgn_pbuf* p) {

@@ -25,8 +25,9 @@ constexpr size_t kTrioLdsMax = 160 * 1024;
 // the two-role kernel's n-step rings: dynamic LDS per workgroup at the most
 constexpr size_t kDuoNstLds = 64 * 1024;
 
-// input selector
-enum { IN_NONE = 0, IN_UNITS = 1, IN_SINGLE = 2, IN_DISCRETE = 3 };
+// input selector (IN_WEIGHTS: A + 1 portfolio weights per env and step, cash
+// first, turned into units in the single-role kernel)
+enum { IN_NONE = 0, IN_UNITS = 1, IN_SINGLE = 2, IN_DISCRETE = 3, IN_WEIGHTS = 4 };
 
 // the fields of mgn_traj a launch stores (traj_mask, mgn_duo.h)
 enum : uint32_t { O_REW = 1u, O_AREW = 2u, O_SHP = 4u, O_DONE = 8u, O_OPR = 16u, O_OPT = 32u,

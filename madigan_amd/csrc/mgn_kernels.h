@@ -41,7 +41,13 @@ struct KParams {
   int shaper, reward_mode, auto_reset, atoms;
   int reqm_one;  // required_margin == 1.0
   int ablate;  // diagnostic timing builds only (mgn_set_ablation); 0 in every real run
-  double eta, cos_temp, unit_size;
+  double eta, cos_temp;
+  // a launch reads one of the two: discrete atoms scale by unit_size, portfolio
+  // weights (IN_WEIGHTS) drop differences below wthresh (0: none)
+  union {
+    double unit_size;
+    double wthresh;
+  };
   double sexp;  // sortino_shaperA/B exponent
   // state
   double *L, *mep, *Bm, *P, *sx, *oum, *dy;
@@ -1498,10 +1504,34 @@ __device__ __forceinline__ void nstep_column(const KParams& p, RingP ring, OutP 
     for (int j = pops; j < n; ++j) out[(size_t)j * D + d] = 0.;
 }
 
+// Portfolio weights -> units (DDPG.action_to_transaction, ddpg.py:183-208;
+// DDPGDiscretized :396-421 with thresh > 0) on the state a step starts from:
+// w0 the cash weight, uc the lane's asset weights (+0.0 in padding slots) on
+// entry and its units on return, eq that state's equity.  The weights are normalised by their sum (entry 0 + the
+// canonical tree over the assets) unless it is zero, ledgerNormedFull
+// (Portfolio.cpp:150-155) is subtracted, differences below thresh are dropped
+// and the rest is scaled to units.  Every quotient is the correctly rounded
+// fp64 one: the units feed the ledger.
+template <int M, int S>
+__device__ __forceinline__ void weights_units(const Lane<M>& s, double w0, double eq, double thresh,
+                                              double (&uc)[M]) {
+  const double sumw = w0 + canon<M, S>(uc);
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const double d = (sumw == 0.) ? uc[m] : uc[m] / sumw;
+    const double c = (s.L[m] * s.P[m]) / eq;
+    double x = d - c;
+    if (thresh > 0. && fabs(x) < thresh) x = 0.;
+    uc[m] = s.valid[m] ? (x * eq) / s.P[m] : 0.;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // The fused step kernel: K consecutive Env steps per launch, state held in
 // registers between steps.  in_kind selects Env::step() / step(units) /
-// step(assetIdx, units) / discrete actions via action_to_transaction.
+// step(assetIdx, units) / discrete actions via action_to_transaction /
+// portfolio weights (WTS, compiled in alone: the kernel then takes no other
+// input kind; units_in holds the weights) via weights_units.
 // RQ1: required_margin == 1.0, where x / required_margin == x exactly and the
 // divisions are skipped.  NST: n-step aggregation (nstep > 1) compiled in.
 // speculative Broker resolution for one asset per lane (defined in mgn_duo.h)
@@ -1511,11 +1541,12 @@ __device__ __forceinline__ void broker_spec(Lane<1>& s, const KParams& p, EnvRec
                                             double (&tu)[1], double (&tc)[1], int (&rk)[1], int ls,
                                             Sums& after, int& any_mc);
 
-template <int M, int S, bool RQ1, bool NST>
-__global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_kind,
+template <int M, int S, bool RQ1, bool NST, bool WTS = false>
+__global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_kind_rt,
                                                 const double* __restrict__ units_in,
                                                 const int32_t* __restrict__ aidx_in,
                                                 const int8_t* __restrict__ act_in, int K) {
+  const int in_kind = WTS ? (int)IN_WEIGHTS : in_kind_rt;
   // loop-invariant fp64 parameters live in VGPRs: the kernel is SGPR-bound
   // (pointers), and an SGPR spill costs a v_readlane per use in the loop
   p.init_cash = in_vgpr(p.init_cash);
@@ -1670,6 +1701,12 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
         const double u = units_in[oN + env];
 #pragma unroll
         for (int m = 0; m < M; ++m) uc[m] = (s.valid[m] && s.asset[m] == ai) ? u : 0.;
+      }
+      if constexpr (WTS) {  // units_in: weights (K, N, A + 1)
+        const double* wrow = units_in + (oN + env) * (size_t)(A + 1);
+#pragma unroll
+        for (int m = 0; m < M; ++m) uc[m] = s.valid[m] ? wrow[1 + s.asset[m]] : 0.;
+        weights_units<M, S>(s, wrow[0], prevEq, p.wthresh, uc);
       }
 #pragma unroll
       for (int m = 0; m < M; ++m) prevVal[m] = s.L[m] * s.P[m];
@@ -2034,6 +2071,30 @@ __global__ __launch_bounds__(BLOCK) void k_valuation(KParams p, double* __restri
   o[7] = bav;
   o[8] = q.lp;
   o[9] = margin_call(q, cash, p.mainM) ? (double)MGN_MARGIN_CALL : (double)MGN_GREEN;
+}
+
+// The units a weights step would order from the current state (weights_units
+// on the equity k_step starts from): w (N, A + 1) -> out (N, A).
+template <int M, int S>
+__global__ __launch_bounds__(BLOCK) void k_weights_units(KParams p, const double* __restrict__ w_in,
+                                                         double* __restrict__ out) {
+  constexpr int EPB = BLOCK / S;
+  const int tid = threadIdx.x;
+  const int ls = tid % S;
+  const int env = blockIdx.x * EPB + tid / S;
+  if (env >= p.N) return;
+  Lane<M> s;
+  load_lane<M>(s, p, env, ls);
+  const double cash = p.cash[env];
+  const Sums q = port_sums<M, S>(s.L, s.mep, s.Bm, s.P);
+  const double* wrow = w_in + (size_t)env * (p.A + 1);
+  double uc[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) uc[m] = s.valid[m] ? wrow[1 + s.asset[m]] : 0.;
+  weights_units<M, S>(s, wrow[0], (cash + q.lp) - q.b, p.wthresh, uc);
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+    if (s.valid[m]) out[(size_t)env * p.A + s.asset[m]] = uc[m];
 }
 
 }  // namespace mgn

@@ -1,7 +1,8 @@
 // mgn_launch.h -- host-side launchers of the templated step kernels.  The
-// kernels are instantiated in 17 translation units (mgn_launch_<unit>.hip:
-// one per padded asset count, and units of their own for instantiations built
-// with other flags) that compile in parallel.  Which kernel runs a launch is
+// kernels are instantiated in 24 translation units (mgn_launch_<unit>.hip:
+// one per padded asset count, units of their own for instantiations built
+// with other flags, and one per padded asset count for the portfolio-weight
+// instantiations) that compile in parallel.  Which kernel runs a launch is
 // decided in mgn_select.h; a unit only maps the choice onto the kernels it
 // instantiates (mgn_units.h) and launches it.
 #pragma once
@@ -47,6 +48,13 @@ struct ValArgs {
   double* out;
   hipStream_t stream;
 };
+// k_weights_units: weights (N, A + 1) -> units (N, A); p.wthresh set by the caller
+struct WtuArgs {
+  KParams p;
+  const double* weights;
+  double* out;
+  hipStream_t stream;
+};
 
 // every unit's one step entry: launches the chosen kernel; false when the unit
 // instantiates none that matches or the device refuses its dynamic LDS size
@@ -54,11 +62,12 @@ struct ValArgs {
 MGN_UNITS(MGN_X)
 #undef MGN_X
 
-// Env construction / reset and valuation: the single-role layout's kernels,
-// m = single_m(APAD, assets per lane)
+// Env construction / reset, valuation and weights -> units: the single-role
+// layout's kernels, m = single_m(APAD, assets per lane)
 #define MGN_DECLARE_APAD(A)                        \
   void launch_init_a##A(int m, const InitArgs& a); \
-  void launch_val_a##A(int m, const ValArgs& a);
+  void launch_val_a##A(int m, const ValArgs& a);   \
+  void launch_wtu_a##A(int m, const WtuArgs& a);
 MGN_DECLARE_APAD(1)
 MGN_DECLARE_APAD(2)
 MGN_DECLARE_APAD(4)

@@ -1,0 +1,3 @@
+// launchers for APAD = 16, portfolio-weight input (see mgn_launch.h)
+#include "mgn_launch_impl.h"
+MGN_DEFINE_UNIT(a16w)

@@ -2,8 +2,8 @@
 // mgn_launch_<unit>.hip).  MGN_DEFINE_UNIT(u) instantiates the kernels of
 // Unit_u's lists (mgn_units.h), each from its named configuration, and defines
 // launch_u, which looks the chosen configuration up in them; it carries no
-// policy (mgn_select.h).  MGN_DEFINE_APAD(A) adds the APAD's init / valuation
-// launchers.
+// policy (mgn_select.h).  MGN_DEFINE_APAD(A) adds the APAD's init / valuation /
+// weights-to-units launchers.
 #pragma once
 
 #include <utility>
@@ -17,7 +17,7 @@ namespace mgn {
 template <class U, size_t I>
 constexpr auto single_kernel() {
   constexpr SingleCfg c = U::single.v[I];
-  return &k_step<c.M, c.S, c.rq1, c.nst>;
+  return &k_step<c.M, c.S, c.rq1, c.nst, c.wts>;
 }
 template <class U, size_t I>
 constexpr auto duo_kernel() {
@@ -93,6 +93,14 @@ struct ValL {
     hipLaunchKernelGGL((k_valuation<M, S>), dim3(grid), dim3(BLOCK), 0, a.stream, a.p, a.out);
   }
 };
+template <int M, int S>
+struct WtuL {
+  static void run(const WtuArgs& a) {
+    const int epb = BLOCK / S;
+    const int grid = (a.p.N + epb - 1) / epb;
+    hipLaunchKernelGGL((k_weights_units<M, S>), dim3(grid), dim3(BLOCK), 0, a.stream, a.p, a.weights, a.out);
+  }
+};
 
 // m = M in {8, 4, 2, 1} within [min_m(APAD), APAD]; S = APAD / M <= 16
 template <template <int, int> class F, int APAD, int M = 8, typename Arg>
@@ -117,4 +125,5 @@ void dispatch_m(int m, const Arg& a) {
   namespace mgn {                                                                            \
   void launch_init_a##A(int m, const InitArgs& a) { dispatch_m<InitL, A>(m, a); }            \
   void launch_val_a##A(int m, const ValArgs& a) { dispatch_m<ValL, A>(m, a); }               \
+  void launch_wtu_a##A(int m, const WtuArgs& a) { dispatch_m<WtuL, A>(m, a); }               \
   }

@@ -38,22 +38,26 @@ struct StepKey {
 enum class Family { Single, Duo, Trio };
 // the translation unit mgn_launch_<name>.hip that instantiates the kernel
 enum Unit { U_NONE = -1, U_A1, U_A2, U_A4, U_A8, U_A16, U_A32, U_A64, U_A1T, U_A1TNST, U_A2NST, U_A4NST,
-            U_A8NST, U_A16NST, U_A8T, U_A8K1, U_A8K1W, U_A16M2, U_COUNT };
+            U_A8NST, U_A16NST, U_A8T, U_A8K1, U_A8K1W, U_A16M2, U_A1W, U_A2W, U_A4W, U_A8W, U_A16W, U_A32W,
+            U_A64W, U_COUNT };
 constexpr const char* kUnitName[U_COUNT] = {"a1", "a2", "a4", "a8", "a16", "a32", "a64", "a1t", "a1tnst",
-                                            "a2nst", "a4nst", "a8nst", "a16nst", "a8t", "a8k1", "a8k1w", "a16m2"};
-// the unit of the padded asset count 1, 2, .., 64 (and, offset by base, of its n-step kernels)
+                                            "a2nst", "a4nst", "a8nst", "a16nst", "a8t", "a8k1", "a8k1w", "a16m2",
+                                            "a1w", "a2w", "a4w", "a8w", "a16w", "a32w", "a64w"};
+// the unit of the padded asset count 1, 2, .., 64 (and, offset by base, of its
+// n-step kernels: U_A1TNST; of its portfolio-weight kernels: U_A1W)
 constexpr Unit apad_unit(int apad, Unit base = U_A1) {
   int i = 0;
   while ((1 << i) < apad) ++i;
   return (Unit)(base + i);
 }
 
-// the template arguments of k_step<M, S, RQ1, NST>, k_step_duo<S, RQ1, ABL,
+// the template arguments of k_step<M, S, RQ1, NST, WTS>, k_step_duo<S, RQ1, ABL,
 // DISC, RP, NST, GK> and k_step_trio<S, RQ1, DISC, OMC, WIN, TW, NST, GK, RP,
 // MM, ONE, K1>, by name (their meaning: mgn_kernels.h, mgn_duo.h, mgn_trio.h)
 struct SingleCfg {
   int M = 1, S = 1;
   bool rq1 = false, nst = false;
+  bool wts = false;  // portfolio-weight input (IN_WEIGHTS) compiled in alone
 };
 struct DuoCfg {
   int S = 2;
@@ -71,7 +75,7 @@ struct TrioCfg {
   bool one = false, k1 = false;
 };
 constexpr bool operator==(const SingleCfg& a, const SingleCfg& b) {
-  return a.M == b.M && a.S == b.S && a.rq1 == b.rq1 && a.nst == b.nst;
+  return a.M == b.M && a.S == b.S && a.rq1 == b.rq1 && a.nst == b.nst && a.wts == b.wts;
 }
 constexpr bool operator==(const DuoCfg& a, const DuoCfg& b) {
   return a.S == b.S && a.rq1 == b.rq1 && a.abl == b.abl && a.disc == b.disc && a.rp == b.rp && a.nst == b.nst &&
@@ -231,7 +235,10 @@ constexpr int auto_m(const StepKey& k) {
 constexpr StepChoice select_single(const StepKey& k) {
   StepChoice c;
   c.family = Family::Single;
-  c.unit = apad_unit(k.apad);
+  // portfolio weights: the instantiations that turn them into units, in
+  // units of their own (a1w .. a64w)
+  c.single.wts = k.in_kind == IN_WEIGHTS;
+  c.unit = apad_unit(k.apad, c.single.wts ? U_A1W : U_A1);
   c.single.M = single_m(k.apad, k.m);
   c.single.S = k.apad / c.single.M;
   c.single.rq1 = k.reqm_one;
@@ -355,6 +362,10 @@ constexpr StepChoice select_trio(const StepKey& k) {
 }
 
 constexpr StepChoice select_step(const StepKey& k) {
+  // portfolio weights: only the single-role kernel turns them into units
+  // (its WTS instantiations), so such a launch runs it at the handle's layout
+  // whatever the schedule (same state, same bits)
+  if (k.in_kind == IN_WEIGHTS) return select_single(k);
   Family f = choose_sched(k);
   if (f == Family::Trio) {
     // a 9..16-asset window handle takes the three-role kernel (automatic

@@ -33,12 +33,13 @@ using SingleList = CfgList<SingleCfg, 16>;
 using DuoList = CfgList<DuoCfg, 20>;
 using TrioList = CfgList<TrioCfg, 36>;
 
-// k_step: every M in {1, 2, 4, 8} within [min_m(APAD), APAD], n = 1 and n-step
-constexpr SingleList single_list(int apad) {
+// k_step: every M in {1, 2, 4, 8} within [min_m(APAD), APAD], n = 1 and n-step;
+// wts: the portfolio-weight instantiations (units a1w .. a64w)
+constexpr SingleList single_list(int apad, bool wts = false) {
   SingleList l;
   for (int M = 8; M >= 1; M /= 2)
     for (int nst = 0; nst < 2; ++nst)
-      if (M >= min_m(apad) && M <= apad) l.add_rq({M, apad / M, false, nst != 0});
+      if (M >= min_m(apad) && M <= apad) l.add_rq({M, apad / M, false, nst != 0, wts});
   return l;
 }
 
@@ -210,6 +211,14 @@ struct UnitTrio {
   static constexpr SingleList single = {};
   static constexpr DuoList duo = {};
 };
+// the portfolio-weight instantiations of k_step at one padded asset count
+template <int APAD>
+struct UnitWts {
+  static constexpr Unit id = apad_unit(APAD, U_A1W);
+  static constexpr SingleList single = single_list(APAD, true);
+  static constexpr DuoList duo = {};
+  static constexpr TrioList trio = {};
+};
 using Unit_a1 = UnitApad<1>;
 using Unit_a2 = UnitApad<2>;
 using Unit_a4 = UnitApad<4>;
@@ -227,11 +236,18 @@ struct Unit_a8t : UnitTrio<U_A8T> { static constexpr TrioList trio = trio_agent8
 struct Unit_a8k1 : UnitTrio<U_A8K1> { static constexpr TrioList trio = trio_agent8_list(true, TRIO_W); };
 struct Unit_a8k1w : UnitTrio<U_A8K1W> { static constexpr TrioList trio = trio_agent8_list(true, 64); };
 struct Unit_a16m2 : UnitTrio<U_A16M2> { static constexpr TrioList trio = trio_m2_list(); };
+using Unit_a1w = UnitWts<1>;
+using Unit_a2w = UnitWts<2>;
+using Unit_a4w = UnitWts<4>;
+using Unit_a8w = UnitWts<8>;
+using Unit_a16w = UnitWts<16>;
+using Unit_a32w = UnitWts<32>;
+using Unit_a64w = UnitWts<64>;
 
 // every unit, in the order of enum Unit
 #define MGN_UNITS(X) \
   X(a1) X(a2) X(a4) X(a8) X(a16) X(a32) X(a64) X(a1t) X(a1tnst) X(a2nst) X(a4nst) X(a8nst) X(a16nst) X(a8t) \
-  X(a8k1) X(a8k1w) X(a16m2)
+  X(a8k1) X(a8k1w) X(a16m2) X(a1w) X(a2w) X(a4w) X(a8w) X(a16w) X(a32w) X(a64w)
 
 // the unit instantiates the chosen kernel
 template <class U>

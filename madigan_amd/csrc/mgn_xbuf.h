@@ -171,6 +171,12 @@ int xbuf_launch_add(const mgn_xbuf& x, const XbLaunch& l, void* stream);
 int xbuf_launch_gather(const mgn_xbuf& x, const int64_t* idx_dev, const mgn_xbuf_batch& b, int64_t n_batch,
                        uint64_t seed, uint64_t call, void* stream);
 int xbuf_launch_clear(const mgn_xbuf& x, int32_t nstep_only, void* stream);
+// portfolio-weight actions: after xbuf_launch_add on the same stream / by the
+// indices of a gather
+int xbuf_launch_add_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const double* weights, const uint8_t* n_shaped,
+                         int32_t K, void* stream);
+int xbuf_launch_gather_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const int64_t* idx_dev, void* out,
+                            int64_t n_batch, void* stream);
 
 }  // namespace mgn
 

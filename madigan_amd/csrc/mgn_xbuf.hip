@@ -317,7 +317,91 @@ __global__ __launch_bounds__(256) void k_xbuf_clear(mgn_xbuf x, int32_t nstep_on
   if (e == 0 && !nstep_only) x.cursor[0] = x.cursor[1] = 0;
 }
 
+// ---- portfolio-weight actions (mgn_xbuf_wact) --------------------------------
+// The float actions of a weights launch go to the slots k_xbuf_copy just
+// filled: the same plan, offsets, base and origin steps, read after the add.
+// A lane per (step, env, column); T the stored type (rounded once from fp64).
+template <class T>
+__global__ __launch_bounds__(256) void k_xbuf_wact_copy(mgn_xbuf x, mgn_xbuf_wact wa, const double* weights,
+                                                         const uint8_t* n_shaped, int32_t K) {
+  const int64_t N = x.n_envs, P = x.n_assets + 1;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)K * N * P) return;
+  const int64_t t = i / P, c = i - t * P;
+  const int32_t k = (int32_t)(t / N);
+  const int64_t e = t - (int64_t)k * N;
+  const int32_t p = x.plan[t];
+  const int32_t pops = xb_pops(p, n_shaped[t]);
+  const int64_t off = x.plan[(size_t)x.plan_steps * N + t], base = x.plan_base[0];
+  T* action = (T*)wa.action;
+  const T* carry = (const T*)wa.carry;
+  for (int32_t j = 0; j < pops; ++j) {
+    const int32_t s = xb_origin(k, p, j);
+    const int64_t slot = xb_slot(base, off, j, x.size);
+    action[slot * P + c] = s >= 0 ? (T)weights[((size_t)s * N + e) * P + c]
+                                  : carry[(e * xb_cn(x) + xb_carry_slot(s, x.nstep)) * P + c];
+  }
+}
+
+// the last n - 1 steps' weights, as k_xbuf_carry keeps the int8 atoms: slot i
+// of the new carry comes from the launch or from a later slot of the old one
+template <class T>
+__global__ __launch_bounds__(256) void k_xbuf_wact_carry(mgn_xbuf x, mgn_xbuf_wact wa, const double* weights,
+                                                          int32_t K) {
+  const int64_t N = x.n_envs, P = x.n_assets + 1;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * P) return;
+  const int64_t e = i / P, c = i - e * P;
+  const int cn = x.nstep - 1;
+  T* carry = (T*)wa.carry + (size_t)e * cn * P;
+  for (int s = 0; s < cn; ++s) {
+    const int32_t st = K + (s - cn);
+    carry[(size_t)s * P + c] = st >= 0 ? (T)weights[((size_t)st * N + e) * P + c] : carry[(size_t)(st + cn) * P + c];
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_xbuf_wact_gather(mgn_xbuf x, mgn_xbuf_wact wa, const int64_t* idx_in,
+                                                           T* out, int64_t n_batch) {
+  const int64_t P = x.n_assets + 1;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_batch * P) return;
+  const int64_t r = i / P, c = i - r * P;
+  int64_t filled = x.cursor[1];
+  if (filled > x.size) filled = x.size;
+  const int64_t idx = idx_in[r];
+  out[i] = (idx >= 0 && idx < filled) ? ((const T*)wa.action)[idx * P + c] : (T)0;
+}
+
 }  // namespace
+
+int xbuf_launch_add_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const double* weights, const uint8_t* n_shaped,
+                         int32_t K, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t P = x.n_assets + 1;
+  const dim3 grid((unsigned)(((int64_t)K * x.n_envs * P + 255) / 256)), cgrid((unsigned)((x.n_envs * P + 255) / 256));
+  if (wa.f32) {
+    hipLaunchKernelGGL(k_xbuf_wact_copy<float>, grid, dim3(256), 0, st, x, wa, weights, n_shaped, K);
+    if (x.nstep > 1) hipLaunchKernelGGL(k_xbuf_wact_carry<float>, cgrid, dim3(256), 0, st, x, wa, weights, K);
+  } else {
+    hipLaunchKernelGGL(k_xbuf_wact_copy<double>, grid, dim3(256), 0, st, x, wa, weights, n_shaped, K);
+    if (x.nstep > 1) hipLaunchKernelGGL(k_xbuf_wact_carry<double>, cgrid, dim3(256), 0, st, x, wa, weights, K);
+  }
+  return (int)hipGetLastError();
+}
+
+int xbuf_launch_gather_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const int64_t* idx_dev, void* out,
+                            int64_t n_batch, void* stream) {
+  const dim3 grid((unsigned)((n_batch * (x.n_assets + 1) + 255) / 256));
+  if (wa.f32) {
+    hipLaunchKernelGGL(k_xbuf_wact_gather<float>, grid, dim3(256), 0, (hipStream_t)stream, x, wa, idx_dev, (float*)out,
+                       n_batch);
+  } else {
+    hipLaunchKernelGGL(k_xbuf_wact_gather<double>, grid, dim3(256), 0, (hipStream_t)stream, x, wa, idx_dev,
+                       (double*)out, n_batch);
+  }
+  return (int)hipGetLastError();
+}
 
 int xbuf_launch_add(const mgn_xbuf& x, const XbLaunch& l, void* stream) {
   const hipStream_t st = (hipStream_t)stream;

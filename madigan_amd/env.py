@@ -633,6 +633,72 @@ class BatchedEnv:
         L.check(self.lib.mgn_rollout_units(self.h, C.c_void_p(u.data_ptr()), K, C.byref(t)), self.h)
         return out
 
+    # ---- portfolio-weight actions (DDPG / DDPGDiscretized) -----------------
+    def launch_weights(self, weights, steps: bool = True):
+        """Portfolio weights as the entry points read them: a contiguous
+        (K, N, A+1) -- ``steps=False``: (N, A+1) -- float64 tensor on the
+        handle's device.  float64 or float32; float32 is widened on the device
+        (exactly), nothing is copied through the host."""
+        torch = _torch()
+        if not isinstance(weights, torch.Tensor):
+            weights = torch.as_tensor(np.asarray(weights))
+        if weights.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"weights must be float64 or float32, got {weights.dtype}")
+        if steps and weights.dim() == 2:  # one step
+            weights = weights[None]
+        if weights.dim() != (3 if steps else 2) or tuple(weights.shape[-2:]) != (self.N, self.A + 1) \
+                or weights.shape[0] < 1:
+            raise ValueError(f"weights must be {'(K, ' if steps else '('}{self.N}, {self.A + 1}), "
+                             f"got {tuple(weights.shape)}")
+        return weights.to(self.device).double().contiguous()
+
+    @staticmethod
+    def _thresh(transaction_thresh) -> float:
+        t = float(transaction_thresh)
+        if not t >= 0.0:
+            raise ValueError(f"transaction_thresh must be a number >= 0, got {transaction_thresh!r}")
+        return t
+
+    def rollout_weights(self, weights, out: Optional[dict] = None, transaction_thresh: float = 0.0) -> dict:
+        """K fused steps from portfolio weights (K,N,A+1), cash first
+        (mgn_rollout_weights; ddpg.py:183-208): each step turns its row into
+        units on the state it starts from, then steps as `rollout_units`.
+        ``transaction_thresh`` > 0 drops weight differences below it
+        (DDPGDiscretized, ddpg.py:396-421)."""
+        thresh = self._thresh(transaction_thresh)
+        w = self.launch_weights(weights)
+        K = int(w.shape[0])
+        own = out is None
+        out = self.alloc_traj(K) if own else out
+        t = self._traj_for(out, K, cache=not own)
+        L.check(self.lib.mgn_rollout_weights(self.h, C.c_void_p(w.data_ptr()), K, thresh, C.byref(t)), self.h)
+        return out
+
+    def rollout_weights_hist(self, weights, out: Optional[dict] = None, transaction_thresh: float = 0.0) -> dict:
+        """`rollout_weights` that also keeps the launch history, as
+        `rollout_hist` does (mgn_rollout_weights_hist)."""
+        if not self.W:
+            raise RuntimeError("env built with window=0")
+        thresh = self._thresh(transaction_thresh)
+        w = self.launch_weights(weights)
+        K = int(w.shape[0])
+        own = out is None
+        out = self.alloc_traj(K) if own else out
+        t = self._traj_for(out, K, cache=not own)
+        L.check(self.lib.mgn_rollout_weights_hist(self.h, C.c_void_p(w.data_ptr()), K, thresh, C.byref(t)), self.h)
+        return out
+
+    def weights_to_units(self, weights, transaction_thresh: float = 0.0):
+        """The (N, A) units the next weights step would order for weights
+        (N, A+1) (mgn_weights_to_units): the agent's logged transaction."""
+        torch = _torch()
+        thresh = self._thresh(transaction_thresh)
+        w = self.launch_weights(weights, steps=False)
+        units = torch.empty((self.N, self.A), dtype=torch.float64, device=self.device)
+        L.check(self.lib.mgn_weights_to_units(self.h, C.c_void_p(w.data_ptr()), thresh,
+                                              C.c_void_p(units.data_ptr())), self.h)
+        return units
+
     def generate_actions(self, k_steps: int, seed: int = 0x6D6164):
         torch = _torch()
         a = torch.empty((k_steps, self.N, self.A), dtype=torch.int8, device=self.device)

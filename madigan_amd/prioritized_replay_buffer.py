@@ -29,8 +29,9 @@ to, which is what prioritized replay intends.  While slot 0 alone is filled
 the reference's seat leaves a zero total: such a sample returns ``idx = -1``,
 weight 0 and zero rows, and the update skips those rows.
 
-The base class's limits hold unchanged (norm none / log windows, discrete
-actions, generator sources).  There is no CPU fallback.
+The base class's limits hold unchanged (norm none / log windows, generator
+sources), and so do its action kinds: with ``action_kind="weights"`` the batch
+carries the float portfolio weights.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -224,9 +225,17 @@ class DevicePrioritizedReplayBuffer(DeviceReplayBuffer):
 def make_buffer_from_config(config, env, **kw):
     """make_buffer_from_config (madigan/utils/buffers/__init__.py:15-21):
     the prioritized buffer when agent_config.prioritized_replay is set, else
-    the uniform one."""
+    the uniform one.  The actor-critic agents (agent_type DDPG,
+    DDPGDiscretized) act with portfolio weights: their buffer stores those
+    (action_kind="weights"), and DDPGDiscretized's collects with
+    agent_config.transaction_thresh."""
     from .env import _cfg_get
     aconf = _cfg_get(config, "agent_config")
+    agent = _cfg_get(config, "agent_type") or _cfg_get(aconf, "agent_type")
+    if agent in ("DDPG", "DDPGDiscretized"):
+        kw.setdefault("action_kind", "weights")
+        if agent == "DDPGDiscretized":
+            kw.setdefault("transaction_thresh", float(_cfg_get(aconf, "transaction_thresh", 0.0) or 0.0))
     if _cfg_get(aconf, "prioritized_replay", False):
         return DevicePrioritizedReplayBuffer.from_config(config, env, **kw)
     return DeviceReplayBuffer.from_config(config, env, **kw)

@@ -24,10 +24,20 @@ right after the clears).  ``clear_nstep()`` (and ``clear()``) go with
 both.
 
 There is no CPU fallback.  The prioritized buffer is
-``prioritized_replay_buffer.DevicePrioritizedReplayBuffer``, a subclass.  Out
-of scope: the recurrent buffer, windows under the per-window normalisers (standard_normal,
-lookback...), continuous-action launches and replay-tape sources (their
-``data_end`` steps, which the reference's loop skips, are not handled).
+``prioritized_replay_buffer.DevicePrioritizedReplayBuffer``, a subclass.
+
+``action_kind="weights"`` is the buffer of the actor-critic agents (DDPG,
+DDPGDiscretized; offpolicy_ac.py:86-137): ``collect(env, weights)`` runs
+``env.rollout_weights_hist`` and ``SARSD.action`` is the (B, A+1) weights row
+of the pop's origin step in ``action_dtype`` (float32 by default, as
+prep_sarsd_tensors casts actions anyway, ddpg.py:236-238), kept beside the
+windows (mgn_xbuf_wact) and carried across launches as the discrete atoms are.
+A buffer takes launches of its own kind only.
+
+Out of scope: the recurrent buffer, windows under the per-window normalisers
+(standard_normal, lookback...), replay-tape sources (their ``data_end`` steps,
+which the reference's loop skips, are not handled) and envs that do not reset
+themselves.
 """
 from __future__ import annotations
 
@@ -40,6 +50,8 @@ from . import _lib as L
 _STORAGE = ("state_price", "state_port", "state_ts", "next_price", "next_port", "next_ts", "action", "reward",
             "done")
 _CARRY = ("cursor", "pending", "carry_rows", "carry_ts", "carry_act", "carry_fill")
+_WACT = ("wact_action", "wact_carry")  # action_kind="weights" (mgn_xbuf_wact)
+ACTION_KINDS = ("discrete", "weights")
 
 
 class SARSD:
@@ -78,7 +90,9 @@ class DeviceReplayBuffer:
     from ``n_envs, n_assets, window, nstep[, n_feats, reward_dim, device]``.
     ``state_dtype=torch.float32`` stores the windows rounded to nearest, as
     prep_state_tensors casts them anyway; timestamps, actions, rewards and
-    flags keep their types.
+    flags keep their types.  ``action_kind="weights"`` (with ``action_dtype``
+    float32 or float64, and a default ``transaction_thresh`` for ``collect``)
+    stores portfolio-weight actions; see the module docstring.
 
     ``sample(B)`` draws index i of its c-th call as ``floor(x * filled / 2^64)``
     of the 64-bit Philox4x32-10 draw x keyed by ``seed`` at counter (c, i):
@@ -87,9 +101,19 @@ class DeviceReplayBuffer:
     """
 
     def __init__(self, size, env=None, *, n_envs=None, n_assets=None, window=None, nstep=None, n_feats=None,
-                 reward_dim=1, device=None, state_dtype=None, seed=0):
+                 reward_dim=1, device=None, state_dtype=None, seed=0, action_kind="discrete", action_dtype=None,
+                 transaction_thresh=0.0):
         import torch
         self.torch = torch
+        if action_kind not in ACTION_KINDS:
+            raise ValueError(f"action_kind must be one of {ACTION_KINDS}, got {action_kind!r}")
+        action_dtype = torch.float32 if action_dtype is None else action_dtype
+        if action_kind == "weights" and action_dtype not in (torch.float32, torch.float64):
+            raise ValueError("action_dtype must be torch.float32 or torch.float64")
+        if not float(transaction_thresh) >= 0.0:
+            raise ValueError(f"transaction_thresh must be a number >= 0, got {transaction_thresh!r}")
+        self.action_kind, self.transaction_thresh = action_kind, float(transaction_thresh)
+        self.action_dtype = action_dtype if action_kind == "weights" else torch.int64
         if env is not None:
             if env.spec.replay:
                 raise ValueError("generator sources only: a replay tape's data_end steps, which the reference's "
@@ -130,17 +154,24 @@ class DeviceReplayBuffer:
                       reward=((S, D), torch.float64), done=((S,), torch.uint8), cursor=((2,), i64),
                       pending=((N,), i32), carry_rows=((N, cn, F + A + 1), torch.float64), carry_ts=((N, cn), i64),
                       carry_act=((N, cn, A), torch.int8), carry_fill=((N, cn), i32), plan_base=((1,), i64))
+        if action_kind == "weights":
+            shapes.update(wact_action=((S, A + 1), action_dtype), wact_carry=((N, cn, A + 1), action_dtype))
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             self._t = {k: torch.zeros(s, dtype=dt, device=self.device) for k, (s, dt) in shapes.items()}
         self._t["plan"] = None
+        self._zero_act = None  # weights launches: the int8 atoms mgn_xbuf_add reads
         d = L.XBuf()
         d.n_envs, d.n_assets, d.n_feats, d.window, d.nstep, d.reward_dim = N, A, F, W, self.nstep, D
         d.state_f32 = int(state_dtype == torch.float32)
         d.size = S
         for k, t in self._t.items():
-            if t is not None:
+            if t is not None and k not in _WACT:
                 setattr(d, k, t.data_ptr())
         self._d = d
+        self._wa = None
+        if action_kind == "weights":
+            self._wa = L.XBufWact(action=self._t["wact_action"].data_ptr(), carry=self._t["wact_carry"].data_ptr(),
+                                  f32=int(action_dtype == torch.float32))
         if env is not None:
             pend = env._t(env._v.nstep_len, i32, (N,)) if env.nstep > 1 else None
             if pend is not None and bool((pend != 0).any()):
@@ -170,30 +201,60 @@ class DeviceReplayBuffer:
             self._d.plan = self._t["plan"].data_ptr()
             self._d.plan_steps = K
 
-    def collect(self, env, actions, out=None):
+    def collect(self, env, actions, out=None, transaction_thresh=None):
         """K x { env.step; preprocessor.stream_state; self.buffer.add(sarsd) }
         (offpolicy_q.py:143, :193-203) in one launch and one add: snapshots
         ``env.ring_len``, runs ``env.rollout_hist(actions, out)`` and adds the
-        launch from its history view.  Returns the trajectory."""
+        launch from its history view.  Returns the trajectory.
+
+        A weights buffer takes (K, N, A+1) portfolio weights instead
+        (offpolicy_ac.py:86-137) and runs ``env.rollout_weights_hist`` with
+        ``transaction_thresh`` (None: the buffer's)."""
         torch = self.torch
         if env.N != self.N or env.A != self.A or env.W != self.W or env.nstep != self.nstep or env.D != self.D \
                 or env.F != self.F:
             raise ValueError("the env's dimensions differ from the buffer's")
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             len0 = env.ring_len.clone()
-        actions = env.launch_actions(actions)
-        out = env.rollout_hist(actions, out)
+        if self.action_kind == "weights":
+            if torch.is_tensor(actions) and not actions.is_floating_point():
+                raise ValueError("a weights buffer takes portfolio-weight launches: (K, N, A+1) float weights")
+            thresh = self.transaction_thresh if transaction_thresh is None else transaction_thresh
+            actions = env.launch_weights(actions)
+            out = env.rollout_weights_hist(actions, out, transaction_thresh=thresh)
+        else:
+            if transaction_thresh is not None:
+                raise ValueError("transaction_thresh goes with a weights buffer (action_kind='weights')")
+            if torch.is_tensor(actions) and actions.is_floating_point():
+                raise ValueError(f"discrete-action launches only: actions must be (K, {self.N}, {self.A}) int8 "
+                                 "(portfolio weights need action_kind='weights')")
+            actions = env.launch_actions(actions)
+            out = env.rollout_hist(actions, out)
         self.add_launch(env.window_hist_view(), len0, actions, out)
         return out
 
     def add_launch(self, view, len0, actions, out):
         """mgn_xbuf_add of a launch the caller ran: ``view`` its
         ``window_hist_view()``, ``len0`` the (N,) int32 window fills before it,
-        ``actions`` its (K, N, A) int8 input, ``out`` its trajectory (``done``,
+        ``actions`` its (K, N, A) int8 input -- for a weights buffer its
+        (K, N, A+1) float64 weights --, ``out`` its trajectory (``done``,
         ``shaped`` and ``n_shaped`` are read)."""
         torch = self.torch
         N, A, W, n, D = self.N, self.A, self.W, self.nstep, self.D
-        if actions.dtype != torch.int8 or actions.dim() != 3 or tuple(actions.shape[1:]) != (N, A):
+        weights = None
+        if self.action_kind == "weights":
+            weights = actions
+            if weights.dtype != torch.float64 or weights.dim() != 3 or tuple(weights.shape[1:]) != (N, A + 1) \
+                    or weights.device != self.device or not weights.is_contiguous():
+                raise ValueError(f"portfolio-weight launches only: weights must be a contiguous (K, {N}, {A + 1}) "
+                                 f"float64 tensor on {self.device}")
+            K = int(weights.shape[0])
+            # mgn_xbuf_add reads (K, N, A) int8 atoms: zeros, into the unused int64 store
+            if self._zero_act is None or self._zero_act.shape[0] < K:
+                with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+                    self._zero_act = torch.zeros((K, N, A), dtype=torch.int8, device=self.device)
+            actions = self._zero_act[:K]
+        elif actions.dtype != torch.int8 or actions.dim() != 3 or tuple(actions.shape[1:]) != (N, A):
             raise ValueError(f"discrete-action launches only: actions must be (K, {N}, {A}) int8")
         K = int(actions.shape[0])
         if self.size < (K + n - 1) * N:
@@ -213,6 +274,9 @@ class DeviceReplayBuffer:
         p = {k: C.c_void_p(t.data_ptr()) for k, (t, _, _) in want.items()}
         L.check(self.lib.mgn_xbuf_add(C.byref(self._d), p["hist"], p["hist_ts"], p["hend"], p["hlen"], p["len0"],
                                       p["actions"], p["done"], p["shaped"], p["n_shaped"], K, self._sp()))
+        if weights is not None:
+            L.check(self.lib.mgn_xbuf_add_wact(C.byref(self._d), C.byref(self._wa), C.c_void_p(weights.data_ptr()),
+                                               p["n_shaped"], K, self._sp()))
 
     # ---- sampling -----------------------------------------------------------
     def _batch(self, B: int):
@@ -222,16 +286,25 @@ class DeviceReplayBuffer:
                       next_price=((B, W, F), sd), next_port=((B, W, A + 1), sd), next_ts=((B, W), torch.int64),
                       action=((B, A), torch.int64), reward=((B, D), torch.float64), done=((B,), torch.uint8),
                       idx=((B,), torch.int64))
+        if self._wa is not None:  # filled by mgn_xbuf_gather_wact from idx (_sarsd)
+            shapes["action"] = ((B, A + 1), self.action_dtype)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             t = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in shapes.items()}
         b = L.XBufBatch()
         if B:
             for k, v in t.items():
-                setattr(b, k, v.data_ptr())
+                if k != "action" or self._wa is None:
+                    setattr(b, k, v.data_ptr())
         return t, b
 
     def _sarsd(self, t):
+        """The SARSD of a gathered batch; a weights buffer first gathers its
+        float actions by the batch's slots (same stream, after the gather)."""
         from .env import State
+        if self._wa is not None and t["idx"].numel():
+            L.check(self.lib.mgn_xbuf_gather_wact(C.byref(self._d), C.byref(self._wa), C.c_void_p(t["idx"].data_ptr()),
+                                                  C.c_void_p(t["action"].data_ptr()), int(t["idx"].numel()),
+                                                  self._sp()))
         reward = t["reward"][:, 0] if self.D == 1 else t["reward"]
         return SARSD(State(t["state_price"], t["state_port"], t["state_ts"]), t["action"], reward,
                      State(t["next_price"], t["next_port"], t["next_ts"]), t["done"].view(self.torch.bool), t["idx"])
@@ -311,19 +384,30 @@ class DeviceReplayBuffer:
         """Storage, cursor, carry and the sample counter, as host arrays: a
         buffer loaded from it continues bit for bit."""
         self.stream.synchronize()
-        sd = {k: self._t[k].cpu().numpy().copy() for k in _STORAGE + _CARRY}
+        sd = {k: self._t[k].cpu().numpy().copy() for k in self._saved()}
+        if self._wa is not None:
+            sd["action_kind"] = self.action_kind
         sd["dims"] = np.array([self.size, self.N, self.A, self.F, self.W, self.nstep, self.D,
                                int(self.state_dtype == self.torch.float32)], dtype=np.int64)
         sd["seed"], sd["sample_calls"] = self.seed, self.sample_calls
         return sd
 
+    def _saved(self):
+        return _STORAGE + _CARRY + (_WACT if self._wa is not None else ())
+
     def load_state_dict(self, sd: dict) -> None:
         torch = self.torch
+        if sd.get("action_kind", "discrete") != self.action_kind:
+            raise ValueError(f"state_dict of a {sd.get('action_kind', 'discrete')!r}-action buffer, this one stores "
+                             f"{self.action_kind!r}")
+        if self._wa is not None and np.asarray(sd["wact_action"]).dtype != \
+                (np.float32 if self.action_dtype == torch.float32 else np.float64):
+            raise ValueError("state_dict of another action_dtype")
         mine = [self.size, self.N, self.A, self.F, self.W, self.nstep, self.D,
                 int(self.state_dtype == torch.float32)]
         if [int(v) for v in sd["dims"]] != mine:
             raise ValueError(f"state_dict of a buffer of dimensions {list(sd['dims'])}, this one has {mine}")
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            for k in _STORAGE + _CARRY:
+            for k in self._saved():
                 self._t[k].copy_(torch.as_tensor(np.asarray(sd[k])).view(self._t[k].shape))
         self.seed, self.sample_calls = int(sd["seed"]), int(sd["sample_calls"])

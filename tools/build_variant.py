@@ -38,7 +38,7 @@ def main():
         obj = os.path.join(out_dir, base.replace(".hip", ".o"))
         # (MGN_VARIANT_NO_UNIT_FLAGS=1: without the unit's own flags, e.g. with
         # machine LICM in a unit the product builds without it)
-        uf = [] if os.environ.get("MGN_VARIANT_NO_UNIT_FLAGS") else B.UNIT_FLAGS.get(base, [])
+        uf = [] if os.environ.get("MGN_VARIANT_NO_UNIT_FLAGS") else B.unit_flags(base)
         subprocess.run([cc, *B.FLAGS, *uf, "-DMGN_DIAG", *extra, "-c", "-o", obj, src], check=True)
         return obj
 
