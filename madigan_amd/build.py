@@ -139,7 +139,7 @@ PROBE_ENTRIES = ("mgp_abi", "mgp_div_by_rcp", "mgp_rt_div", "mgp_rt_sqrt", "mgp_
 
 def build_math_probe(force: bool = False, verbose: bool = False) -> str:
     """tests/_probe/libmgn_math_probe.so: the device math helpers of
-    mgn_math.h / mgn_kernels.h behind element-wise kernels, for
+    mgn_math.h / mgn_shapers.h / mgn_reduce.h behind element-wise kernels, for
     tests/test_gpu_math_probe.py.  Test infrastructure: compiled with exactly
     the product's FLAGS, never linked into or loaded by the product library."""
     deps_ = [PROBE_SRC] + glob.glob(os.path.join(CSRC, "*.h"))

@@ -2,8 +2,15 @@
 // included by exactly one translation unit (mgn_api.hip).
 #pragma once
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/madigan_amd.h"
+#include "mgn_consts.h"
 #include "mgn_gather_plan.h"
-#include "mgn_kernels.h"
+#include "mgn_math.h"
+#include "mgn_params.h"
+#include "mgn_reduce.h"
 
 namespace mgn {
 

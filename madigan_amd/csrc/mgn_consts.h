@@ -29,7 +29,7 @@ constexpr size_t kDuoNstLds = 64 * 1024;
 // first, turned into units in the single-role kernel)
 enum { IN_NONE = 0, IN_UNITS = 1, IN_SINGLE = 2, IN_DISCRETE = 3, IN_WEIGHTS = 4 };
 
-// the fields of mgn_traj a launch stores (traj_mask, mgn_duo.h)
+// the fields of mgn_traj a launch stores (traj_mask, mgn_params.h)
 enum : uint32_t { O_REW = 1u, O_AREW = 2u, O_SHP = 4u, O_DONE = 8u, O_OPR = 16u, O_OPT = 32u,
                   O_TS = 64u, O_TP = 128u, O_TU = 256u, O_TC = 512u, O_RISK = 1024u,
                   O_MC = 2048u, O_NSH = 4096u, O_DEND = 8192u };

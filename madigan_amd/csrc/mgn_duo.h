@@ -31,7 +31,21 @@
 // ticks, 4 the generator side's step finish (outputs).
 #pragma once
 
-#include "mgn_kernels.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/madigan_amd.h"
+#include "mgn_broker.h"
+#include "mgn_consts.h"
+#include "mgn_diag.h"
+#include "mgn_gout.h"
+#include "mgn_lane.h"
+#include "mgn_math.h"
+#include "mgn_params.h"
+#include "mgn_reduce.h"
+#include "mgn_rows.h"
+#include "mgn_shapers.h"
+#include "mgn_sources.h"
 
 namespace mgn {
 
@@ -63,82 +77,6 @@ struct DuoShared {
                        // cleared two barriers after its last read)
 };
 
-// Output pointers live in VGPR pairs (in_vgpr: the compiler cannot move them
-// back into SGPRs) and their null tests in one uniform bit mask: with every
-// pointer of KParams and mgn_traj in SGPRs the kernel spilled SGPRs to VGPR
-// lanes and reloaded them with v_readlane inside the step loop.  The VGPR
-// pointers are typed address_space(1) (global): a pointer whose provenance
-// the compiler cannot see is otherwise generic, its accesses become FLAT
-// instructions, and FLAT counts on lgkmcnt as well as vmcnt -- every LDS
-// wait and every barrier of the step loop then waited for the previous
-// stores (and the next action's load) to complete in memory.
-// (the O_* field bits and the output sets O_STD / O_ALL / O_STDN / O_WSTD: mgn_consts.h)
-__host__ __device__ __forceinline__ uint32_t traj_mask(const mgn_traj& o) {
-  return (o.reward ? O_REW : 0u) | (o.agent_reward ? O_AREW : 0u) | (o.shaped ? O_SHP : 0u) |
-         (o.done ? O_DONE : 0u) | (o.obs_price ? O_OPR : 0u) | (o.obs_port ? O_OPT : 0u) |
-         (o.timestamp ? O_TS : 0u) | (o.tprice ? O_TP : 0u) | (o.tunits ? O_TU : 0u) |
-         (o.tcost ? O_TC : 0u) | (o.risk ? O_RISK : 0u) | (o.margin_call ? O_MC : 0u) |
-         (o.n_shaped ? O_NSH : 0u) | (o.data_end ? O_DEND : 0u);
-}
-#define MGN_G __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ MGN_G T* vptr(T* q) {
-  return (MGN_G T*)in_vgpr(reinterpret_cast<uintptr_t>(q));
-}
-template <typename T>
-__device__ __forceinline__ const MGN_G T* vptr(const T* q) {
-  return (const MGN_G T*)in_vgpr(reinterpret_cast<uintptr_t>(q));
-}
-struct GTraj {
-  MGN_G double *reward, *agent_reward, *shaped;
-  MGN_G uint8_t* done;
-  MGN_G double *obs_price, *obs_port;
-  MGN_G uint64_t* timestamp;
-  MGN_G double *tprice, *tunits, *tcost;
-  MGN_G uint8_t *risk, *margin_call, *n_shaped, *data_end;
-};
-// OMC != 0: the output set is known at compile time; the pointers of the
-// fields outside it are never loaded
-template <uint32_t OMC = 0>
-__device__ __forceinline__ GTraj traj_vgpr(const mgn_traj& o) {
-  constexpr uint32_t M = OMC ? OMC : ~0u;
-  GTraj v = {};
-  if (M & O_REW) v.reward = vptr(o.reward);
-  if (M & O_AREW) v.agent_reward = vptr(o.agent_reward);
-  if (M & O_SHP) v.shaped = vptr(o.shaped);
-  if (M & O_DONE) v.done = vptr(o.done);
-  if (M & O_OPR) v.obs_price = vptr(o.obs_price);
-  if (M & O_OPT) v.obs_port = vptr(o.obs_port);
-  if (M & O_TS) v.timestamp = vptr(o.timestamp);
-  if (M & O_TP) v.tprice = vptr(o.tprice);
-  if (M & O_TU) v.tunits = vptr(o.tunits);
-  if (M & O_TC) v.tcost = vptr(o.tcost);
-  if (M & O_RISK) v.risk = vptr(o.risk);
-  if (M & O_MC) v.margin_call = vptr(o.margin_call);
-  if (M & O_NSH) v.n_shaped = vptr(o.n_shaped);
-  if (M & O_DEND) v.data_end = vptr(o.data_end);
-  return v;
-}
-// element index k * stride + base as one 32 x 32 + 64 multiply-add (the
-// host checks that every stride fits 32 bits)
-__device__ __forceinline__ size_t kidx(int k, uint32_t stride, size_t base) {
-  return (size_t)(uint32_t)k * stride + base;
-}
-// output stores (written once per launch, read after it)
-template <typename T>
-__device__ __forceinline__ void ost(MGN_G T* q, T v) {
-#if defined(MGN_ABL_NOSTORE)  // diagnostic timing build: outputs not stored
-  (void)q; (void)v;
-#else
-  *q = v;
-#endif
-}
-// the generator side's per-env state outputs, global VGPR pointers
-struct GState {
-  MGN_G double *epstats, *ring, *hist;
-  MGN_G uint64_t *ring_ts, *hist_ts;
-};
-
 // One-step shaping (DSR / DDR / PPC / naive, n = 1) runs on the ledger side,
 // right after the step's reward (on the generator side it measured slower at
 // C3, 2.79 -> 2.95 us per step at 256-step launches, round 1).
@@ -155,10 +93,6 @@ struct GenOut {
   double ep_ret, ep_len, n_done;
   int32_t head, len;
   int32_t hcnt, klast;  // launch history: next row, the step its rows belong to
-};
-// the ledger side's shaper state (nstep_buffer.py:38-60) and PPC constants
-struct LedOut {
-  double shA, shB, cos_qn;
 };
 
 // the finish of step k on the ledger side (its post-tick quantities in
@@ -221,14 +155,6 @@ __device__ __forceinline__ void ledger_finish(DuoRec<S>& rc, const Lane<1>& s, c
     rc.rCos[el] = cos_term;
   }
 }
-
-// replay (RP): the State's tape row, this lane's feature value and the row's
-// dataEnd flag (HDFSourceSingle, DataSource.cpp:391-398)
-struct RpCur {
-  double curF;
-  int64_t row;
-  uint32_t dend;
-};
 
 // State.price of the record's State into dst (put_feats): the tape's feature
 // row for replay (one column per lane when F <= S, else read back per column),
@@ -426,450 +352,6 @@ __device__ __forceinline__ void duo_store(const DuoRec<S>& sh, const Lane<1>& s,
       g.head = p.W - 1;
     }
   }
-}
-
-// The cash chain of one pass of broker_spec under its guess (Broker.cpp:
-// 128-135: cash becomes ((cash + X1) - y) - Z when an order executes), systolic over
-// DPP (row_shr:1 -- a segment of S <= 16 lanes lies in one 16-lane row): lane
-// i holds order i's terms, masked once per pass to the additions' identities
-// where the guess skips the order ((c + -0.0) - 0.0 - 0.0 == c, bit for bit,
-// -0.0 and NaN included); in every step each lane applies its order to the
-// cash it holds and hands the result to lane i + 1, while the segment's first
-// lane keeps cash0.  After step t the lanes 0..t + 1 hold their final values
-// (lane i: the serial c_i = step(c_(i-1), order i-1), one chain_step per
-// order as the serial form), so S - 1 steps leave every lane its cash before
-// its own order, with no LDS round trip (the first lane's walk over the
-// records in LDS, round 4, cost ~1450 cycles per iteration at C3) and no
-// per-step select of the executing orders (masking the terms was 2-5 %
-// slower on round 4's one-lane walk, profiles/r04_ab_chain_mask.txt, where it
-// replaced one select per order).  M orders per lane (two-slot
-// layout): the lane's orders in slot order within its step.  c_own[m]: the
-// cash before the lane's order m; cend: after the last order (the segment's
-// last lane's).
-// PLAIN (broker_spec's plain wave): every order of the wave has X1 == -0.0
-// and Z == +0.0 by their bits, so the step is c - y alone: x + (-0.0) == x
-// and x - (+0.0) == x for every x, signed zeros included, and a NaN cash
-// still passes through c - y as it does through the general form
-template <int S, int M, bool PLAIN = false>
-__device__ __forceinline__ void dpp_chain(double cash0, const OwnChk (&own)[M], const bool (&gown)[M], int ls,
-                                          double (&c_own)[M], double& cend) {
-  double X1[M], y[M], Z[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    X1[m] = gown[m] ? own[m].X1 : -0.0;
-    y[m] = gown[m] ? own[m].y : 0.0;
-    Z[m] = gown[m] ? own[m].Z : 0.0;
-  }
-  auto apply = [&](double c, double (&mid)[M]) {
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      mid[m] = c;
-      if constexpr (PLAIN) c = c - y[m];
-      else c = ((c + X1[m]) - y[m]) - Z[m];
-    }
-    return c;
-  };
-  double v = cash0, mid[M];
-#pragma unroll
-  for (int t = 0; t + 1 < S; ++t) {
-    const double sh = dpp_f64<0x111>(apply(v, mid));  // row_shr:1
-    v = (ls == 0) ? cash0 : sh;
-  }
-  cend = seg_bcast<S, S - 1>(apply(v, mid));
-#pragma unroll
-  for (int m = 0; m < M; ++m) c_own[m] = mid[m];
-}
-
-// The canonical trees of broker_spec in registers: every lane
-// holds its own order's four leaves before (pre) and after (post) the order;
-// the tree of lane ls's check has post leaves for the executed orders j < ls
-// and pre leaves elsewhere.  Level by level, a lane takes its sibling
-// subtree's two versions over DPP -- P (post leaves where executed) and Q
-// (all pre) -- and adds the one its check needs to its own path (the sibling
-// lies left: P, right: Q), while P and Q of the joined subtree are formed
-// for the next level (row_half_mirror / row_mirror reach the sibling half of
-// 8 / 16 lanes: its lanes all hold the same subtree values by then).  Each
-// node is the sum of the same two children as the heap tree's (IEEE addition
-// commutes), so the sums are bit-identical to the LDS form; the root of P is
-// the sums after every executed order.
-// ONE (a one-asset env on S = 2 lanes): the tree is lane 0's one leaf; every
-// lane of the segment takes lane 0's root (its path is only read by lane 0,
-// whose order is the only one).
-// NQ < 4 (broker_spec's plain wave): only the first NQ sums are formed; the
-// leaves of the others are +0.0 in every lane of the wave, before and after
-// the orders, and a tree of +0.0 leaves sums to +0.0 under every guess, so
-// their paths and roots are +0.0 without the additions
-template <int S, bool ONE = false, int NQ = 4>
-__device__ __forceinline__ void dpp_tree4(const double (&pre)[4], const double (&post)[4], bool go_own, int ls,
-                                          double (&path)[4], double (&rootP)[4]) {
-  double nP[NQ], nQ[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    path[q] = pre[q];
-    nQ[q] = pre[q];
-    nP[q] = go_own ? post[q] : pre[q];
-  }
-#pragma unroll
-  for (int q = NQ; q < 4; ++q) path[q] = rootP[q] = 0.0;
-  if constexpr (ONE) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) rootP[q] = seg_bcast<S, 0>(nP[q]);
-    return;
-  }
-  auto level = [&](auto sibP, auto sibQ, bool right) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const double sp = sibP(nP[q]), sq = sibQ(nQ[q]);
-      path[q] = path[q] + (right ? sp : sq);
-      nP[q] = nP[q] + sp;
-      nQ[q] = nQ[q] + sq;
-    }
-  };
-  if constexpr (S >= 2)
-    level([](double v) { return dpp_f64<0xB1>(v); }, [](double v) { return dpp_f64<0xB1>(v); }, (ls & 1) != 0);
-  if constexpr (S >= 4)
-    level([](double v) { return dpp_f64<0x4E>(v); }, [](double v) { return dpp_f64<0x4E>(v); }, (ls & 2) != 0);
-  if constexpr (S >= 8)
-    level([](double v) { return dpp_f64<0x141>(v); }, [](double v) { return dpp_f64<0x141>(v); }, (ls & 4) != 0);
-  if constexpr (S >= 16)
-    level([](double v) { return dpp_f64<0x140>(v); }, [](double v) { return dpp_f64<0x140>(v); }, (ls & 8) != 0);
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) rootP[q] = nP[q];
-}
-
-// The passes of broker_spec: guess, check every order under the guess, fix
-// the first wrong guess, repeat.  PLAIN: the wave's plain form (broker_spec);
-// the same statements on the same operands, with dpp_tree4 over the first two
-// sums and dpp_chain's one-term step.  t_tr / t_ch: the stamp builds' times
-// of the first pass after the trees and after the chain (unused otherwise)
-template <int S, bool RQ1, bool ONE, bool PLAIN>
-__device__ __forceinline__ void spec_passes(const KParams& p, const double (&lf_pre)[4], const double (&lf_post)[4],
-                                            const OwnChk (&oc)[1], int act, uint32_t act_bits, double cash0, int ls,
-                                            int& go, int& mc, int& insuff, double& cend, double (&rootP)[4],
-                                            unsigned long long& t_tr, unsigned long long& t_ch) {
-  const OwnChk& own = oc[0];
-  uint32_t go_bits = act_bits;  // the guess
-  for (int it = 0; it <= S; ++it) {
-    // canonical sums before this lane's order: leaves of executed earlier
-    // orders after the order, the others before
-    double r[4];
-    dpp_tree4<S, ONE, PLAIN ? 2 : 4>(lf_pre, lf_post, ((go_bits >> ls) & 1) != 0, ls, r, rootP);
-#ifdef MGN_STAMPS
-    if (it == 0) t_tr = __builtin_amdgcn_s_memtime();
-#endif
-    // cash before this lane's order, and after the last order, under the
-    // guess (dpp_chain)
-    double cown1[1];
-    {
-      const bool g1[1] = {((go_bits >> ls) & 1) != 0};
-      dpp_chain<S, 1, PLAIN>(cash0, oc, g1, ls, cown1, cend);
-    }
-    const double c_own = cown1[0];
-#ifdef MGN_STAMPS
-    if (it == 0) t_ch = __builtin_amdgcn_s_memtime();
-#endif
-    // Portfolio::checkRisk(i, u), Portfolio.cpp:254-279 (as XRounds)
-    const double pnl = r[0] - r[1];
-    const double balance = c_own + r[2];
-    const double bp = balance + pnl;
-    const double availM = RQ1 ? bp : bp / p.reqM;
-    const double equity = (c_own + r[0]) - r[3];
-    const double mr = p.mainM * pnl;
-    mc = (own.need_mc != 0) & ((equity <= -mr) | (bp <= -mr));
-    insuff = (own.need_insuff != 0) & ((availM <= own.aPX) | (balance <= 0.));
-    go = act & !mc & !insuff;
-    const uint32_t bad = (uint32_t)seg_or<S>((go != (int)((go_bits >> ls) & 1)) ? (1 << ls) : 0);
-#ifdef MGN_STAMPS
-    if (threadIdx.x == DUO_HALF) s_duo_sub[6] += 1;  // passes of the wave
-#endif
-    if (bad == 0) break;
-    const int i0 = __builtin_ctz(bad);
-    const uint32_t go_now = (uint32_t)seg_or<S>(go << ls);
-    const uint32_t below = (1u << i0) - 1u;
-    go_bits = (go_bits & below) | (go_now & (1u << i0)) | (act_bits & ~(below | (1u << i0)));
-  }
-}
-
-// Broker::handleTransaction(units) for a segment of S lanes, one asset per
-// lane, resolved speculatively.  The serial dependency between orders (each
-// risk check sees the cash and portfolio sums the earlier orders left,
-// Broker.cpp:149-155) is only a dependency on which earlier orders executed.
-// Guess that every nonzero order executes; then each lane checks ITS order
-// against the state the guess implies -- the cash chain c_i over the earlier
-// executed orders (the same (((c + X1) - y) - Z) sequence as the serial form)
-// and the canonical trees over the leaves (executed earlier orders: post-order
-// leaves, the rest: pre-order) -- all lanes in parallel.  The checks up to the
-// first order whose outcome contradicts the guess are exact; that order's
-// outcome is taken from its check, later ones are re-guessed, repeat.  Every
-// check that is kept was evaluated on exactly the operands the serial form
-// uses, so the ledger, responses and sums are bit-identical to XRounds; an
-// unrefused batch (the common case) costs one pass instead of S dependent
-// rounds.
-// The plain wave.  With no short position the sh leaves L (meanEntry [L < 0])
-// are +0.0, at required_margin == 1 the borrowed leaves are (amt - amt 1 =
-// +0.0), X1 is -0.0 unless an order closes through a position and Z is +0.0
-// unless borrowed margin is settled: half the trees then sum zeros and two of
-// the chain's three additions are identities.  One test per call, on the
-// bits of the lanes' own operands (they do not change between passes),
-// balloted over the wave -- its active lanes are whole env segments -- asks
-// whether every sh / b leaf, pre and post, and every Z is +0.0 and every X1
-// is -0.0; a -0.0 leaf, a NaN or any other value makes the wave general, and
-// a general wave runs the full passes.  A plain wave's passes are
-// bit-identical to them:
-//  * a sum of +0.0 leaves is +0.0 under every guess (dpp_tree4's NQ = 2
-//    sets those paths and roots without the additions);
-//  * x + (-0.0) == x and x - (+0.0) == x for every x, signed zeros
-//    included, so ((c + X1) - y) - Z == c - y (dpp_chain's PLAIN step; a
-//    skipped order's y is masked to +0.0 in both forms);
-//  * a NaN cash value still passes through c - y in both forms.
-// MGN_ABL_PLAIN_OFF (diagnostic builds) forces the general passes
-template <int S, bool RQ1, bool ONE>
-__device__ __forceinline__ void broker_spec(Lane<1>& s, const KParams& p, EnvRecs<S>& er,
-                                            double& cash, const double (&uc)[1], double (&tp)[1],
-                                            double (&tu)[1], double (&tc)[1], int (&rk)[1], int ls,
-                                            Sums& after, int& any_mc) {
-  double cu2[1], me2[1], bm3[1], tpr[1], tco[1];
-#ifdef MGN_STAMPS
-  const unsigned long long t_a = __builtin_amdgcn_s_memtime();
-#endif
-  double lf_pre[4], lf_post[4];  // the own leaves and check operands, in registers
-  OwnChk oc[1];
-  order_prep<1, S, false>(s, p, er, uc, ls, cu2, me2, bm3, tpr, tco, lf_pre, lf_post, oc);
-#ifdef MGN_STAMPS
-  const unsigned long long t_b = __builtin_amdgcn_s_memtime();
-#endif
-  const int act = uc[0] != 0. ? 1 : 0;
-  const uint32_t act_bits = (uint32_t)seg_or<S>(act << ls);
-  const double cash0 = cash;
-  int go = 0, mc = 0, insuff = 0;
-  double cend = cash0;
-  double rootP[4];  // the sums after the orders the pass took
-  unsigned long long t_tr = 0, t_ch = 0;  // stamp builds
-  // the plain wave's test: any set bit in a lane makes the wave general
-  const long long gen_bits = __double_as_longlong(lf_pre[2]) | __double_as_longlong(lf_post[2]) |
-                             __double_as_longlong(lf_pre[3]) | __double_as_longlong(lf_post[3]) |
-                             __double_as_longlong(oc[0].Z) |
-                             (__double_as_longlong(oc[0].X1) ^ (long long)(1ull << 63));
-  if (!kAblPlainOff && __ballot(gen_bits != 0) == 0)
-    spec_passes<S, RQ1, ONE, true>(p, lf_pre, lf_post, oc, act, act_bits, cash0, ls, go, mc, insuff, cend,
-                                   rootP, t_tr, t_ch);
-  else
-    spec_passes<S, RQ1, ONE, false>(p, lf_pre, lf_post, oc, act, act_bits, cash0, ls, go, mc, insuff, cend,
-                                    rootP, t_tr, t_ch);
-  cash = cend;
-#ifdef MGN_STAMPS
-  const unsigned long long t_c = __builtin_amdgcn_s_memtime();
-#endif
-  any_mc = seg_or<S>(act & mc) != 0;
-  rk[0] = act ? (mc ? MGN_MARGIN_CALL : (insuff ? MGN_INSUFF_MARGIN : MGN_GREEN)) : rk[0];
-  const bool go_own[1] = {go != 0};
-  // the post-transaction sums: the root of the last pass's P tree (its guess
-  // held for every order)
-  after.lp = rootP[0];
-  after.ml = rootP[1];
-  after.sh = rootP[2];
-  after.b = rootP[3];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  apply_orders<1>(s, go_own, cu2, me2, bm3, tpr, tco, uc, tp, tu, tc);
-#ifdef MGN_STAMPS
-  const unsigned long long t_d = __builtin_amdgcn_s_memtime();
-  if (threadIdx.x == DUO_HALF) {
-    s_duo_sub[0] += t_b - t_a;
-    s_duo_sub[1] += t_c - t_b;
-    s_duo_sub[2] += t_d - t_c;
-    s_duo_sub[3] += t_tr - t_b;   // first pass: the DPP trees
-    s_duo_sub[4] += t_ch - t_tr;  // first pass: the cash chain, published and read back
-    s_duo_sub[7] += t_c - t_ch;   // the checks and the remaining passes
-    s_duo_sub[5] += 1;  // broker calls
-  }
-#endif
-}
-
-// broker_spec with two orders per lane (slots 2 ls, 2 ls + 1 of a 2 S-asset
-// env: the three-role kernel's 16-asset layout on 8 lanes).  The canonical
-// tree's first level is the lane's own pair, formed in registers: the check
-// of slot 0 reads the pair pre + pre, slot 1 (post of slot 0 where it
-// executes) + pre, and the pair's P / Q versions go on to dpp_tree4's
-// cross-lane levels, which add the same sibling to both slots' paths.  The
-// cash chain is dpp_chain's with the lane's two orders per step; the fix-up
-// of a wrong guess is broker_spec's
-// (the first order whose check disagrees decides, the later ones are guessed
-// again), so the result is the sequential Broker's.
-template <int S, bool RQ1>
-__device__ __forceinline__ void broker_spec_m2(Lane<2>& s, const KParams& p, EnvRecs<2 * S>& er, double& cash,
-                                               const double (&uc)[2], double (&tp)[2], double (&tu)[2],
-                                               double (&tc)[2], int (&rk)[2], int ls, Sums& after, int& any_mc) {
-  constexpr int M = 2, APAD = 2 * S;
-  double cu2[M], me2[M], bm3[M], tpr[M], tco[M];
-  double lf_pre[4 * M], lf_post[4 * M];
-  OwnChk oc[M];
-  order_prep<M, S, false>(s, p, er, uc, ls, cu2, me2, bm3, tpr, tco, lf_pre, lf_post, oc);
-  // the leaves are re-formed in every pass from the slot state the lane
-  // holds anyway (ledger, price, and the order's outcome): the same products
-  // (order_prep's), so the same bits, without 16 leaf registers live across
-  // the passes (the 168-register budget)
-  auto leaves = [&](int m, double (&pr)[4], double (&po)[4]) {
-    double L0 = s.L[m], me0 = s.mep[m], bm0 = s.Bm[m], P = s.P[m], c2 = cu2[m], e2 = me2[m], b2 = bm3[m];
-    asm volatile("" : "+v"(L0), "+v"(me0), "+v"(bm0), "+v"(P), "+v"(c2), "+v"(e2), "+v"(b2));
-    const double mk0 = (L0 < 0.) ? 1.0 : 0.0;
-    const double mk1 = (c2 < 0.) ? 1.0 : 0.0;
-    pr[0] = L0 * P;
-    pr[1] = me0 * L0;
-    pr[2] = L0 * (me0 * mk0);
-    pr[3] = bm0;
-    po[0] = c2 * P;
-    po[1] = e2 * c2;
-    po[2] = c2 * (e2 * mk1);
-    po[3] = b2;
-  };
-  const int sh0 = ls * M;
-  int act[M];
-  act[0] = uc[0] != 0. ? 1 : 0;
-  act[1] = uc[1] != 0. ? 1 : 0;
-  const uint32_t act_bits = (uint32_t)seg_or<S>((act[0] << sh0) | (act[1] << (sh0 + 1)));
-  uint32_t go_bits = act_bits;  // the guess
-  const double cash0 = cash;
-  int go[M] = {0, 0}, mc[M] = {0, 0}, insuff[M] = {0, 0};
-  double cend = cash0;
-  double rootP[4];
-  for (int it = 0; it <= APAD; ++it) {
-    const bool g0 = ((go_bits >> sh0) & 1) != 0, g1 = ((go_bits >> (sh0 + 1)) & 1) != 0;
-    double path0[4], path1[4];
-    {
-      double nP[4], nQ[4], pr0[4], po0[4], pr1[4], po1[4];
-      leaves(0, pr0, po0);
-      leaves(1, pr1, po1);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double a0 = pr0[q], a1 = pr1[q];
-        const double b0 = g0 ? po0[q] : a0;
-        nQ[q] = a0 + a1;
-        path0[q] = nQ[q];
-        path1[q] = b0 + a1;
-        nP[q] = b0 + (g1 ? po1[q] : a1);
-      }
-      auto level = [&](auto sib, bool right) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const double sp = sib(nP[q]), sq = sib(nQ[q]);
-          const double add = right ? sp : sq;
-          path0[q] = path0[q] + add;
-          path1[q] = path1[q] + add;
-          nP[q] = nP[q] + sp;
-          nQ[q] = nQ[q] + sq;
-        }
-      };
-      if constexpr (S >= 2) level([](double v) { return dpp_f64<0xB1>(v); }, (ls & 1) != 0);
-      if constexpr (S >= 4) level([](double v) { return dpp_f64<0x4E>(v); }, (ls & 2) != 0);
-      if constexpr (S >= 8) level([](double v) { return dpp_f64<0x141>(v); }, (ls & 4) != 0);
-      if constexpr (S >= 16) level([](double v) { return dpp_f64<0x140>(v); }, (ls & 8) != 0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) rootP[q] = nP[q];
-    }
-    double cownm[M];
-    {
-      const bool gm[M] = {g0, g1};
-      dpp_chain<S, M>(cash0, oc, gm, ls, cownm, cend);
-    }
-    uint32_t badm = 0, gom = 0;
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const double* r = m == 0 ? path0 : path1;
-      const double c_own = cownm[m];
-      // Portfolio::checkRisk(i, u), Portfolio.cpp:254-279 (as XRounds)
-      const double pnl = r[0] - r[1];
-      const double balance = c_own + r[2];
-      const double bp = balance + pnl;
-      const double availM = RQ1 ? bp : bp / p.reqM;
-      const double equity = (c_own + r[0]) - r[3];
-      const double mr = p.mainM * pnl;
-      mc[m] = (oc[m].need_mc != 0) & ((equity <= -mr) | (bp <= -mr));
-      insuff[m] = (oc[m].need_insuff != 0) & ((availM <= oc[m].aPX) | (balance <= 0.));
-      go[m] = act[m] & !mc[m] & !insuff[m];
-      badm |= (go[m] != (int)((go_bits >> (sh0 + m)) & 1)) ? (1u << (sh0 + m)) : 0u;
-      gom |= (uint32_t)go[m] << (sh0 + m);
-    }
-    const uint32_t bad = (uint32_t)seg_or<S>((int)badm);
-#ifdef MGN_STAMPS
-    if (threadIdx.x == DUO_HALF) s_duo_sub[6] += 1;  // passes of the wave
-#endif
-    if (bad == 0) break;
-    const int i0 = __builtin_ctz(bad);
-    const uint32_t go_now = (uint32_t)seg_or<S>((int)gom);
-    const uint32_t below = (1u << i0) - 1u;
-    go_bits = (go_bits & below) | (go_now & (1u << i0)) | (act_bits & ~(below | (1u << i0)));
-  }
-  cash = cend;
-  any_mc = seg_or<S>((act[0] & mc[0]) | (act[1] & mc[1])) != 0;
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-    rk[m] = act[m] ? (mc[m] ? MGN_MARGIN_CALL : (insuff[m] ? MGN_INSUFF_MARGIN : MGN_GREEN)) : rk[m];
-  const bool go_own[M] = {go[0] != 0, go[1] != 0};
-  after.lp = rootP[0];
-  after.ml = rootP[1];
-  after.sh = rootP[2];
-  after.b = rootP[3];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  apply_orders<M>(s, go_own, cu2, me2, bm3, tpr, tco, uc, tp, tu, tc);
-#ifdef MGN_STAMPS
-  if (threadIdx.x == DUO_HALF) s_duo_sub[5] += 1;  // broker calls
-#endif
-}
-
-// The kernel arguments (KParams + mgn_traj, ~640 bytes) are read through the
-// scalar cache in chunks the register allocator interleaves with their uses,
-// each chunk a dependent miss on a cold cache at launch (~1.7 us of the
-// prologue measured).  One scalar load per 64-byte line, all in flight
-// together, warms every line for the cost of one miss.
-template <int BYTES>
-__device__ __forceinline__ void warm_kernargs() {
-  static_assert(BYTES <= 12 * 64, "one operand per line below");
-  const __attribute__((address_space(4))) uint32_t* ka =
-      (const __attribute__((address_space(4))) uint32_t*)__builtin_amdgcn_kernarg_segment_ptr();
-  constexpr int L = (BYTES + 63) / 64;
-  uint32_t x[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) x[i] = ka[(i < L ? i : L - 1) * 16];
-  // one consumer of every line: the loads issue together, one wait
-  asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]), "s"(x[5]), "s"(x[6]),
-               "s"(x[7]), "s"(x[8]), "s"(x[9]), "s"(x[10]), "s"(x[11]));
-}
-
-// HDFSourceSingle::getData on the tape (gen_tick's replay branch): the row
-// iterCache / loadData would serve, then advance (wrap = the reference's
-// rewind to boundsIdx_.first, DataSource.cpp:368-371, :397-399).  The next
-// row's price, feature, timestamp and dataEnd flag are loaded here for the
-// next tick, so a tick's tape reads leave the step's dependency chain.
-struct RpNext {
-  double P, F;
-  uint64_t ts;
-  uint32_t dend;
-};
-__device__ __forceinline__ void duo_replay_tick(Lane<1>& s, const KParams& p, uint64_t& ts,
-                                                RpCur& cur, RpNext& nx) {
-  const int64_t row = s.rcur;
-  const bool fown = s.fcol >= 0 && s.fcol < p.F;
-  if (s.pf_ok) {
-    if (s.valid[0]) s.P[0] = nx.P;
-    if (fown) cur.curF = nx.F;
-    ts = nx.ts;
-    cur.dend = nx.dend;
-  } else {
-    if (s.valid[0]) s.P[0] = p.rp_price[(size_t)row * p.A + s.asset[0]];
-    if (fown) cur.curF = p.rp_feat[(size_t)row * p.F + s.fcol];
-    ts = p.rp_ts[row];
-    cur.dend = p.rp_end[row];
-  }
-  cur.row = row;
-  s.row = row;
-  s.rcur = (row + 1 == p.rp_rows) ? 0 : row + 1;
-  if (s.valid[0]) nx.P = p.rp_price[(size_t)s.rcur * p.A + s.asset[0]];
-  if (fown) nx.F = p.rp_feat[(size_t)s.rcur * p.F + s.fcol];
-  nx.ts = p.rp_ts[s.rcur];
-  nx.dend = p.rp_end[s.rcur];
-  s.pf_ok = true;
 }
 
 // ABL: the diagnostic ablation build (mgn_set_ablation != 0); the product

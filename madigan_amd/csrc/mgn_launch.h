@@ -10,8 +10,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
-#include "mgn_duo.h"
-#include "mgn_kernels.h"
+#include "../../include/madigan_amd.h"
+#include "mgn_params.h"
 #include "mgn_units.h"
 
 namespace mgn {

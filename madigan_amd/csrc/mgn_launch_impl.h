@@ -8,6 +8,9 @@
 
 #include <utility>
 
+#include "mgn_consts.h"
+#include "mgn_duo.h"
+#include "mgn_kernels.h"
 #include "mgn_launch.h"
 #include "mgn_trio.h"
 

@@ -406,6 +406,9 @@ __device__ __forceinline__ double log_ratio(double x) {
 
 __device__ __forceinline__ double frac_part(double x) { return copysign(x - trunc(x), x); }
 
+// StackerDiscrete's log normaliser (preprocessor.py:79-81)
+__device__ __forceinline__ double log_norm(double x) { return log((x < 1e-5) ? 1e-5 : x); }
+
 // fdlibm e_asin.c on |x| <= 1 (same statements as the oracle's orc_asin)
 __device__ __noinline__ double det_asin(double x) {
   const double pio2_hi = bits_to_d(0x3FF921FB54442D18ull), pio2_lo = bits_to_d(0x3C91A62633145C07ull),

@@ -16,6 +16,7 @@
 #include "../../include/madigan_amd.h"
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define MGN_RN_HD __host__ __device__ __forceinline__
 #else
 #define MGN_RN_HD inline

@@ -46,8 +46,22 @@
 // after an auto-reset); k_step_duo / k_step run the rest.
 #pragma once
 
-#include "mgn_duo.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/madigan_amd.h"
+#include "mgn_broker.h"
+#include "mgn_consts.h"
+#include "mgn_diag.h"
+#include "mgn_gout.h"
+#include "mgn_lane.h"
+#include "mgn_math.h"
+#include "mgn_params.h"
+#include "mgn_reduce.h"
+#include "mgn_rows.h"
 #include "mgn_select.h"
+#include "mgn_shapers.h"
+#include "mgn_sources.h"
 
 namespace mgn {
 
@@ -167,55 +181,6 @@ constexpr size_t trio_static_lds() {
 MGN_LDS_IS(2, 64); MGN_LDS_IS(2, TRIO_W); MGN_LDS_IS(4, 64); MGN_LDS_IS(4, TRIO_W);
 MGN_LDS_IS(8, 64); MGN_LDS_IS(8, TRIO_W); MGN_LDS_IS(16, 64); MGN_LDS_IS(16, TRIO_W);
 #undef MGN_LDS_IS
-
-// The replay tape's tick for the lane's M slots (duo_replay_tick's, per slot:
-// feature column fcol + m when the row's features are spread one per slot)
-template <int M>
-struct RpCurM {
-  double curF[M];
-  int64_t row;
-  uint32_t dend;
-};
-template <int M>
-struct RpNextM {
-  double P[M], F[M];
-  uint64_t ts;
-  uint32_t dend;
-};
-template <int M>
-__device__ __forceinline__ void trio_replay_tick(Lane<M>& s, const KParams& p, uint64_t& ts, RpCurM<M>& cur,
-                                                 RpNextM<M>& nx) {
-  const int64_t row = s.rcur;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const bool fown = s.fcol >= 0 && s.fcol + m < p.F;
-    if (s.pf_ok) {
-      if (s.valid[m]) s.P[m] = nx.P[m];
-      if (fown) cur.curF[m] = nx.F[m];
-    } else {
-      if (s.valid[m]) s.P[m] = p.rp_price[(size_t)row * p.A + s.asset[m]];
-      if (fown) cur.curF[m] = p.rp_feat[(size_t)row * p.F + s.fcol + m];
-    }
-  }
-  if (s.pf_ok) {
-    ts = nx.ts;
-    cur.dend = nx.dend;
-  } else {
-    ts = p.rp_ts[row];
-    cur.dend = p.rp_end[row];
-  }
-  cur.row = row;
-  s.row = row;
-  s.rcur = (row + 1 == p.rp_rows) ? 0 : row + 1;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    if (s.valid[m]) nx.P[m] = p.rp_price[(size_t)s.rcur * p.A + s.asset[m]];
-    if (s.fcol >= 0 && s.fcol + m < p.F) nx.F[m] = p.rp_feat[(size_t)s.rcur * p.F + s.fcol + m];
-  }
-  nx.ts = p.rp_ts[s.rcur];
-  nx.dend = p.rp_end[s.rcur];
-  s.pf_ok = true;
-}
 
 // OMC: the output set when known at compile time (O_ALL, O_STD), else 0.
 // WIN: the handle keeps a window (StackerDiscrete ring, and the launch

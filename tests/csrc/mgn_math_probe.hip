@@ -11,7 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mgn_kernels.h"
+#include "mgn_math.h"
+#include "mgn_reduce.h"
+#include "mgn_shapers.h"
 
 namespace {
 

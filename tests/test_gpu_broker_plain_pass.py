@@ -1,4 +1,4 @@
-"""The speculative Broker's plain pass (broker_spec, csrc/mgn_duo.h): a wave
+"""The speculative Broker's plain pass (broker_spec, csrc/mgn_broker.h): a wave
 in which no lane holds a short or a borrowed position, closes through a
 position or settles borrowed margin runs its passes over two of the four
 canonical trees and with the cash chain's one-term step; every other wave runs

@@ -1,6 +1,6 @@
 """The device math helpers, called directly on operands chosen to break them.
 
-mgn_math.h and the shaper summands of mgn_kernels.h are otherwise exercised
+mgn_math.h and the shaper summands of mgn_shapers.h are otherwise exercised
 only through whole-environment rollouts, which feed them ordinary operands.
 tests/csrc/mgn_math_probe.hip (built by build() into tests/_probe, with the
 product's flags) puts each helper behind an element-wise kernel; these tests
@@ -720,7 +720,7 @@ def _leaves(rng, envs, apad):
 def test_g_canon_bitwise(probe, M, S, one):
     """Every lane of a segment ends with the bits of orc_canon_sum over the
     segment's leaves in asset order; asset a is slot m of lane ls with
-    a = ls * M + m (the loaders: mgn_kernels.h:665, mgn_trio.h:337).  ONE: the
+    a = ls * M + m (the loaders: load_lane, mgn_lane.h, and k_step_trio's, mgn_trio.h).  ONE: the
     env's one asset is lane 0's, lane 1 a pad whose value must not matter, and
     a -0.0 leaf gives -0.0."""
     rng = np.random.default_rng(100 * M + S + int(one))

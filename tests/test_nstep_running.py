@@ -1,4 +1,4 @@
-"""The running-sum n-step pop (MGN_NSTEP_POP_RUNNING, csrc/mgn_kernels.h
+"""The running-sum n-step pop (MGN_NSTEP_POP_RUNNING, csrc/mgn_shapers.h
 nrun_*), restated here in numpy (the kernel's algebra: the same sums, slides and re-sums), against
 the reference's own pops: the golden vectors tests/golden/make_golden.py made
 from madigan/utils/buffers/nstep_buffer.py (DSR :30-98, DDR :101-169, cosine
