@@ -49,6 +49,9 @@
  *                     prefix-sum sampling and the priority update
  *                     (madigan/utils/buffers/prioritized_replay_buffer.py:13-87,
  *                     segment_tree.py:7-66)
+ *   mgn_tear_*        the test episode's record and its tearsheet
+ *                     (madigan/utils/metrics.py:83-175 test_summary;
+ *                     offpolicy_q.py:254-274 test_episode)
  *   mgn_get_views    zero-copy property views (env.cpp:897-913)
  *   mgn_last_error    pybind11 exception translation (DataTypes.h:36-46)
  *
@@ -297,6 +300,46 @@ typedef struct {
   uint8_t *zero_var;
 } mgn_rnorm;
 
+/* Test-episode tearsheet (madigan/utils/metrics.py:83-175 test_summary over the
+ * record of offpolicy_q.py:254-274 test_episode), one episode per env,
+ * caller-owned device memory and no handle.  New symbols only: no existing
+ * struct or function changed, so MGN_ABI_VERSION stays 11.
+ *   ts         (max_steps, n_envs) int64   stored series, time-major: row
+ *   equity     (max_steps, n_envs)         len[e] of column e is env e's next
+ *   prices     (max_steps, n_envs, A)      free row
+ *   len        (n_envs) int32   steps recorded
+ *   active     (n_envs)         1 until the env's done step has been recorded
+ *   sum_equity, sum_reward, sum_tcost (n_envs)  sequential sums from +0.0, in
+ *              time order (sum_tcost: in asset order within a step)
+ *   peak, valley (n_envs)       the expanding maximum of the equity and the
+ *              smallest equity / peak so far (_drawdowns, metrics.py:413-421)
+ *   pos_count  (n_envs, A) int32   steps with ledger != 0 (:123-129)
+ *   overflow   (1) int32        set by mgn_tear_record where an active env had
+ *              no free row (the step is dropped); cleared by mgn_tear_reset */
+typedef struct {
+  int32_t n_envs, n_assets, max_steps, reserved_;
+  int64_t *ts;
+  double *equity;
+  double *prices;
+  int32_t *len;
+  uint8_t *active;
+  double *sum_equity, *sum_reward, *sum_tcost;
+  double *peak, *valley;
+  int32_t *pos_count;
+  int32_t *overflow;
+} mgn_tear;
+/* rows of mgn_tear_summary's (n_out, n_envs) block, A assets and n_tf
+ * timeframes (T < n_tf, a < A): the seven scalars, then
+ *   MGN_TEAR_SCALARS + a                            time_spent_in_pos[a]
+ *   MGN_TEAR_SCALARS + A + T                        equity_returns[T]
+ *   MGN_TEAR_SCALARS + A + n_tf + T                 equity_sharpe[T]
+ *   MGN_TEAR_SCALARS + A + 2 * n_tf + T             equity_sortino[T]
+ *   MGN_TEAR_SCALARS + A + 3 * n_tf + a * n_tf + T  beta[a][T]
+ * n_out = MGN_TEAR_SCALARS + A + 3 * n_tf + A * n_tf */
+enum { MGN_TEAR_MEAN_EQUITY = 0, MGN_TEAR_FINAL_EQUITY = 1, MGN_TEAR_MEAN_REWARD = 2,
+       MGN_TEAR_MAX_DRAWDOWN = 3, MGN_TEAR_MEAN_TCOST = 4, MGN_TEAR_TOTAL_TCOST = 5,
+       MGN_TEAR_NSTEPS = 6, MGN_TEAR_SCALARS = 7 };
+
 /* Uniform experience replay on the device (madigan/utils/buffers/
  * replay_buffer.py:23-172), fed from a launch's outputs and launch history,
  * caller-owned device memory.  mgn_xbuf, mgn_xbuf_batch and the mgn_xbuf_*
@@ -541,6 +584,46 @@ int mgn_rnorm_reset(const mgn_rnorm *rnorm, const uint8_t *mask_dev, void *strea
  * (the reference's window-1 forms divide by zero). */
 int mgn_rnorm_stream(const mgn_rnorm *rnorm, const double *reward_dev, const uint8_t *done_dev,
                      double *out_dev, int32_t k_steps, void *stream);
+/* Start an episode on the descriptor's memory: len = 0, active = 1, the sums
+ * and counts zero, valley = +inf, peak = -inf, overflow = 0.  The series keep
+ * their values: no row at or beyond len is ever read. */
+int mgn_tear_reset(const mgn_tear *tear, void *stream);
+/* One step of test_episode's record (offpolicy_q.py:260-272) for every env
+ * that is still active, one lane per env: ts_dev (n_envs) int64, equity_dev,
+ * reward_dev (n_envs), prices_dev, ledger_dev, tcost_dev (n_envs, A), done_dev
+ * (n_envs).  Env e writes row len[e] of its series, adds to its sums, moves its
+ * peak and valley, counts its nonzero ledger entries, then leaves the episode
+ * where done_dev[e] != 0 -- the done step itself is recorded.  Inactive envs
+ * are not touched.  An active env with len[e] == max_steps is not written and
+ * sets overflow. */
+int mgn_tear_record(const mgn_tear *tear, const int64_t *ts_dev, const double *equity_dev,
+                    const double *reward_dev, const double *prices_dev, const double *ledger_dev,
+                    const double *tcost_dev, const uint8_t *done_dev, void *stream);
+/* test_summary (metrics.py:83-175) of every env's record so far: out_dev
+ * (n_out, n_envs) fp64, rows as listed at MGN_TEAR_*; timeframes_dev (n_tf)
+ * int64 offsets in the timestamps' unit (may be NULL when n_tf is 0).  With
+ * n = len[e]: mean_equity, mean_reward = the streamed sum / n;
+ * total_transaction_cost the streamed sum, mean_ = total / (n * A);
+ * max_drawdown the smallest equity / expanding peak; time_spent_in_pos[a] =
+ * pos_count / n; n = 0 gives NaN everywhere but nsteps = 0.  A timeframe above
+ * (ts[n-1] - ts[0]) / 10 (:111), or below 1, gives NaN in its three return rows
+ * and its betas.  Otherwise x_r = det_log(equity[r] / equity[l]) over
+ * _returns(closed_left=False)'s two-pointer walk of the timestamps (:386-397;
+ * NaN where the walk gives no l, or where the ratio is not a positive normal
+ * number -- np.log's -inf at 0 is the one deviation), y_r likewise of
+ * prices[.][a], and with cnt the non-NaN returns, m their mean:
+ *   equity_returns = m;  equity_sharpe = std == 0 ? 0 : m / std with std =
+ *   sqrt(sum (x - m)^2 / (cnt - 1));  equity_sortino = D == 0 ? (m > 0 ? 50 : 0)
+ *   : min(m / D, 50) with D = sum_{x < 0} x^2 / (n - 1);  beta = C / V with C =
+ *   sum |x - m| |y - my| / (n - 1), V = sum (y - my)^2 / (cnt_y - 1)
+ * -- the reference's formulas as written (:334-364, :296-299, :327-331).  All
+ * fp64, every sum one accumulator from +0.0 in ascending time.
+ * All three calls run on `stream` and do not synchronise the host.
+ * MGN_ERR_CONFIG before any HIP call: a null descriptor or array, n_envs,
+ * n_assets or max_steps < 1, n_tf < 0.  (The timeframes lie in device memory,
+ * so the host cannot refuse one below 1: the kernel drops it as above.) */
+int mgn_tear_summary(const mgn_tear *tear, const int64_t *timeframes_dev, int32_t n_tf, double *out_dev,
+                     void *stream);
 /* K x ReplayBuffer.add of every env in one call (replay_buffer.py:68-90 with
  * NStepBuffer.pop_nstep_sarsd, nstep_buffer.py:342-361; the agent's
  * self.buffer.add(sarsd), offpolicy_q.py:196-203), fed from a launch:

@@ -7,11 +7,13 @@ libmadigan_hip.so); this package is the host side mirroring the reference's
 Python surface (madigan/environments, madigan/utils/preprocessor.py).
 """
 from . import _lib
+from . import metrics
 from . import reward_normalization
 from .config import ConfigError, SourceSpec, replay_spec, spec_from_config
 from .env import (Asset, BatchedEnv, BrokerResponse, DataSourceTick, Env, EnvInfo, RiskInfo, State,
                   get_env_info, make_batched_env, make_env)
 from .hdf import HDFSourceSingle, write_hdf
+from .metrics import EpisodeRecorder, make_timeframes
 from .replay_buffer import DeviceReplayBuffer
 from .prioritized_replay_buffer import DevicePrioritizedReplayBuffer, make_buffer_from_config
 from .preprocessor import (MultiStackerDiscrete, PreProcessor, StackerDiscrete, StackerDiscretePairs,
@@ -19,9 +21,9 @@ from .preprocessor import (MultiStackerDiscrete, PreProcessor, StackerDiscrete, 
 
 __all__ = ["Asset", "BatchedEnv", "BrokerResponse", "ConfigError", "DataSourceTick", "DevicePrioritizedReplayBuffer",
            "DeviceReplayBuffer", "Env",
-           "EnvInfo", "HDFSourceSingle", "PreProcessor", "RiskInfo", "SourceSpec",
+           "EnvInfo", "EpisodeRecorder", "HDFSourceSingle", "PreProcessor", "RiskInfo", "SourceSpec",
            "StackerDiscrete", "State", "get_env_info", "make_batched_env", "make_buffer_from_config", "make_env",
-           "make_preprocessor", "MultiStackerDiscrete", "StackerDiscretePairs",
+           "make_preprocessor", "make_timeframes", "MultiStackerDiscrete", "StackerDiscretePairs",
            "StackerDiscreteReturns", "replay_spec", "spec_from_config", "write_hdf"]
 
 

@@ -107,6 +107,17 @@ class RNorm(C.Structure):  # mgn_rnorm
                 ("weights", C.c_void_p), ("zero_var", C.c_void_p)]
 
 
+class Tear(C.Structure):  # mgn_tear
+    _fields_ = [(n, C.c_int32) for n in ("n_envs", "n_assets", "max_steps", "reserved_")] + [
+        (n, C.c_void_p) for n in ("ts", "equity", "prices", "len", "active", "sum_equity", "sum_reward", "sum_tcost",
+                                  "peak", "valley", "pos_count", "overflow")]
+
+
+# rows of mgn_tear_summary's (n_out, n_envs) block (MGN_TEAR_*)
+TEAR_SCALARS = ("mean_equity", "final_equity", "mean_reward", "max_drawdown", "mean_transaction_cost",
+                "total_transaction_cost", "nsteps")
+
+
 class XBuf(C.Structure):  # mgn_xbuf
     _fields_ = [(n, C.c_int32) for n in ("n_envs", "n_assets", "n_feats", "window", "nstep", "reward_dim",
                                          "state_f32", "plan_steps")] + [("size", C.c_int64)] + [
@@ -177,6 +188,9 @@ SYMBOLS = {
     "mgn_feat_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "mgn_rnorm_reset": (C.c_int, [C.POINTER(RNorm), C.c_void_p, C.c_void_p]),
     "mgn_rnorm_stream": (C.c_int, [C.POINTER(RNorm), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mgn_tear_reset": (C.c_int, [C.POINTER(Tear), C.c_void_p]),
+    "mgn_tear_record": (C.c_int, [C.POINTER(Tear)] + [C.c_void_p] * 8),
+    "mgn_tear_summary": (C.c_int, [C.POINTER(Tear), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgn_xbuf_add": (C.c_int, [C.POINTER(XBuf)] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]),
     "mgn_xbuf_sample": (C.c_int, [C.POINTER(XBuf), C.POINTER(XBufBatch), C.c_int64, C.c_uint64, C.c_uint64,
                                   C.c_void_p]),

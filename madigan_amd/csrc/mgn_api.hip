@@ -20,6 +20,7 @@
 #include "mgn_gather_plan.h"
 #include "mgn_launch.h"
 #include "mgn_rnorm.h"
+#include "mgn_tear.h"
 #include "mgn_pbuf.h"
 #include "mgn_xbuf.h"
 
@@ -1103,6 +1104,49 @@ int mgn_rnorm_stream(const mgn_rnorm* r, const double* reward_dev, const uint8_t
   if (k_steps < 1) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: k_steps must be >= 1");
   return check_hip(nullptr, (hipError_t)mgn::rnorm_launch_stream(*r, reward_dev, done_dev, out_dev, k_steps, stream),
                    "mgn_rnorm_stream");
+}
+
+static int tear_ok(const mgn_tear* t) {
+  if (!t) return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet");
+  if (t->n_envs < 1 || t->n_assets < 1 || t->max_steps < 1)
+    return fail(nullptr, MGN_ERR_CONFIG, "tearsheet: n_envs, n_assets and max_steps must be >= 1");
+  if (!t->ts || !t->equity || !t->prices) return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet series");
+  if (!t->len || !t->active || !t->sum_equity || !t->sum_reward || !t->sum_tcost || !t->peak || !t->valley ||
+      !t->pos_count || !t->overflow)
+    return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet state");
+  return MGN_OK;
+}
+
+int mgn_tear_reset(const mgn_tear* t, void* stream) {
+  int rc = tear_ok(t);
+  if (rc != MGN_OK) return rc;
+  return check_hip(nullptr, (hipError_t)mgn::tear_launch_reset(*t, stream), "mgn_tear_reset");
+}
+
+int mgn_tear_record(const mgn_tear* t, const int64_t* ts_dev, const double* equity_dev, const double* reward_dev,
+                    const double* prices_dev, const double* ledger_dev, const double* tcost_dev,
+                    const uint8_t* done_dev, void* stream) {
+  int rc = tear_ok(t);
+  if (rc != MGN_OK) return rc;
+  if (!ts_dev || !equity_dev || !reward_dev || !prices_dev || !ledger_dev || !tcost_dev || !done_dev)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_record: null step array");
+  return check_hip(nullptr,
+                   (hipError_t)mgn::tear_launch_record(*t, ts_dev, equity_dev, reward_dev, prices_dev, ledger_dev,
+                                                       tcost_dev, done_dev, stream),
+                   "mgn_tear_record");
+}
+
+int mgn_tear_summary(const mgn_tear* t, const int64_t* timeframes_dev, int32_t n_tf, double* out_dev, void* stream) {
+  int rc = tear_ok(t);
+  if (rc != MGN_OK) return rc;
+  if (n_tf < 0) return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: n_tf must be >= 0");
+  if (!out_dev || (n_tf > 0 && !timeframes_dev))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: null timeframes or output");
+  // one lane per (asset, timeframe, env), 64 to a workgroup: the grid's x extent
+  if ((int64_t)t->n_envs * t->n_assets * (n_tf > 0 ? n_tf : 1) / 64 >= INT32_MAX)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: n_envs * n_assets * n_tf exceeds the launch grid");
+  return check_hip(nullptr, (hipError_t)mgn::tear_launch_summary(*t, timeframes_dev, n_tf, out_dev, stream),
+                   "mgn_tear_summary");
 }
 
 static int xbuf_ok(const mgn_xbuf* x) {
