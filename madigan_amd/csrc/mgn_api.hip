@@ -16,13 +16,11 @@
 #include <vector>
 
 #include "../../include/madigan_amd.h"
+#include "mgn_arena.h"
 #include "mgn_aux_kernels.h"
 #include "mgn_gather_plan.h"
 #include "mgn_launch.h"
-#include "mgn_rnorm.h"
-#include "mgn_tear.h"
-#include "mgn_pbuf.h"
-#include "mgn_xbuf.h"
+#include "mgn_status.h"
 
 namespace {
 
@@ -32,16 +30,6 @@ constexpr int kHistStepsPerGroup = 16;
 constexpr size_t kHistGroupBytes = 80 * 1024;  // k_hist_gather: output bytes per workgroup to reach
 
 thread_local std::string g_error;
-
-// bump allocator over the arena: every buffer 256-B aligned
-struct Layout {
-  size_t total = 0;
-  size_t add(size_t bytes) {
-    const size_t o = total;
-    total += (bytes + 255) & ~size_t(255);
-    return o;
-  }
-};
 
 int next_pow2(int a) {
   int p = 1;
@@ -99,76 +87,7 @@ struct mgn_env {
   size_t ag_rows = 0;
 };
 
-namespace {
-
-struct Offsets {
-  size_t L, mep, Bm, P, sx, oum, dy, tlen, tfl, cash, ts, dskip, sA, sB, ep, epstats, ext, units, aidx,
-      ring, ring_ts, rhead, rlen, wprice, wport, wts, mask, reward, areward, shaped, done, obsp,
-      obsport, obsts, tprice, tunits, tcost, risk, mcall, nshaped, dend, nring, nlen, nhead, disc,
-      src, target, rcur, aux;
-  size_t total;
-};
-
-Offsets plan(const mgn_config* c) {
-  const size_t N = (size_t)c->n_envs, A = (size_t)c->n_assets;
-  const size_t W = (size_t)(c->window > 0 ? c->window : 0);
-  const size_t D = (c->reward_mode == MGN_REWARD_AGENT_PER_ASSET) ? A : 1;
-  const size_t n = (size_t)(c->nstep > 0 ? c->nstep : 1);
-  const size_t F = (size_t)(c->n_feats > 0 ? c->n_feats : c->n_assets);
-  Layout l;
-  Offsets o;
-  o.L = l.add(N * A * 8);
-  o.mep = l.add(N * A * 8);
-  o.Bm = l.add(N * A * 8);
-  o.P = l.add(N * A * 8);
-  o.sx = l.add(N * A * 8);
-  o.oum = l.add(N * A * 8);
-  o.dy = l.add(N * A * 8);
-  o.tlen = l.add(N * A * 4);
-  o.tfl = l.add(N * A);
-  o.cash = l.add(N * 8);
-  o.ts = l.add(N * 8);
-  o.dskip = l.add(N * 8);
-  o.sA = l.add(N * D * 8);
-  o.sB = l.add(N * D * 8);
-  o.ep = l.add(N * 2 * 8);
-  o.epstats = l.add(N * 4 * 8);
-  o.ext = l.add(N * A * 8);
-  o.units = l.add(N * A * 8);
-  o.aidx = l.add(N * 4);
-  o.ring = l.add(N * W * (F + A + 1) * 8);
-  o.ring_ts = l.add(N * W * 8);
-  o.rhead = l.add(N * 4);
-  o.rlen = l.add(N * 4);
-  o.wprice = l.add(N * W * F * 8);
-  o.wport = l.add(N * W * (A + 1) * 8);
-  o.wts = l.add(N * W * 8);
-  o.mask = l.add(N);
-  o.reward = l.add(N * 8);
-  o.areward = l.add(N * D * 8);
-  o.shaped = l.add(N * n * D * 8);
-  o.done = l.add(N);
-  o.obsp = l.add(N * F * 8);
-  o.obsport = l.add(N * (A + 1) * 8);
-  o.obsts = l.add(N * 8);
-  o.tprice = l.add(N * A * 8);
-  o.tunits = l.add(N * A * 8);
-  o.tcost = l.add(N * A * 8);
-  o.risk = l.add(N * A);
-  o.mcall = l.add(N);
-  o.nshaped = l.add(N);
-  o.dend = l.add(N);
-  o.nring = l.add(n > 1 ? N * n * D * 8 : 0);
-  o.nlen = l.add(N * 4);
-  o.nhead = l.add(N * 4);
-  o.disc = l.add(2 * n * 8);  // gamma^i, then (sortino_shaperB's running pop) (gamma^i)^(1/exp)
-  o.src = l.add(A * sizeof(mgn_asset_source));
-  o.target = l.add((A + 1) * 8);
-  o.rcur = l.add(N * 8);
-  o.aux = l.add(c->aux ? N * A * MGN_AUX_WIDTH * 8 : 0);
-  o.total = l.total;
-  return o;
-}
+namespace mgn {
 
 int fail(mgn_env* e, int code, const std::string& msg) {
   if (e) e->err = msg;
@@ -180,6 +99,13 @@ int check_hip(mgn_env* e, hipError_t st, const char* what) {
   if (st == hipSuccess) return MGN_OK;
   return fail(e, MGN_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(st));
 }
+
+}  // namespace mgn
+
+namespace {
+
+using mgn::check_hip;
+using mgn::fail;
 
 // the status of a step launch: launch_step's own error, else HIP's last
 int check_step(mgn_env* e, hipError_t st, const char* what) {
@@ -316,9 +242,6 @@ mgn::KParams kparams(const mgn_env* e) {
   p.src = e->src_dev; p.src_g = e->src_dev; p.target = e->target_dev;
   p.nstep = c.nstep; p.nring = v.nstep_ring; p.nlen = v.nstep_len; p.nhead = v.nstep_head;
   p.disc = e->disc_dev;
-  // MGN_NSTEP_POP_RUNNING: the shapers with a running-sum pop, scalar
-  // rewards, and a discount whose slides stay well conditioned (the sums'
-  // rounding grows by 1/gamma per pop between the re-sums every n pops)
   p.nst_run = e->nst_run ? 1 : 0;
   p.nst_rg = p.nst_run ? 1.0 / c.discount : 0.;
   p.nst_rg2 = (p.nst_run && c.shaper == MGN_SHAPER_SORTINO_B) ? 1.0 / std::pow(c.discount, 1.0 / c.sortino_exp) : 0.;
@@ -373,8 +296,17 @@ template <typename Arg>
 void launch(void (*const* fns)(int, const Arg&), const mgn_env* e, const Arg& a) {
   fns[mgn::apad_unit(e->apad)](mgn::single_m(e->apad, e->m), a);
 }
-void (*const kInit[7])(int, const mgn::InitArgs&) = {mgn::launch_init_a1, mgn::launch_init_a2, mgn::launch_init_a4, mgn::launch_init_a8, mgn::launch_init_a16, mgn::launch_init_a32, mgn::launch_init_a64};
-void (*const kVal[7])(int, const mgn::ValArgs&) = {mgn::launch_val_a1, mgn::launch_val_a2, mgn::launch_val_a4, mgn::launch_val_a8, mgn::launch_val_a16, mgn::launch_val_a32, mgn::launch_val_a64};
+// every padded asset count's init, valuation and weights -> units entries, by mgn::apad_unit
+#define MGN_X(A) mgn::launch_init_a##A,
+void (*const kInit[])(int, const mgn::InitArgs&) = {MGN_APADS(MGN_X)};
+#undef MGN_X
+#define MGN_X(A) mgn::launch_val_a##A,
+void (*const kVal[])(int, const mgn::ValArgs&) = {MGN_APADS(MGN_X)};
+#undef MGN_X
+#define MGN_X(A) mgn::launch_wtu_a##A,
+void (*const kWtu[])(int, const mgn::WtuArgs&) = {MGN_APADS(MGN_X)};
+#undef MGN_X
+static_assert(sizeof(kInit) / sizeof(kInit[0]) == mgn::apad_unit(MGN_MAX_ASSETS) + 1, "MGN_APADS reaches MGN_MAX_ASSETS");
 
 // launches the step kernel mgn_select.h chooses.  A choice no unit serves, or
 // a dynamic LDS size the device refuses, is an error (the caller's check_hip
@@ -404,7 +336,6 @@ void launch_val(const mgn_env* e, double* out) {
   mgn::ValArgs a{kparams(e), out, e->stream};
   launch(kVal, e, a);
 }
-void (*const kWtu[7])(int, const mgn::WtuArgs&) = {mgn::launch_wtu_a1, mgn::launch_wtu_a2, mgn::launch_wtu_a4, mgn::launch_wtu_a8, mgn::launch_wtu_a16, mgn::launch_wtu_a32, mgn::launch_wtu_a64};
 void launch_wtu(const mgn_env* e, const double* weights, double thresh, double* out) {
   mgn::WtuArgs a{kparams(e), weights, out, e->stream};
   a.p.wthresh = thresh;
@@ -453,7 +384,7 @@ int mgn_abi_version(void) { return MGN_ABI_VERSION; }
 
 size_t mgn_arena_bytes(const mgn_config* cfg) {
   if (!cfg || cfg->n_envs < 1 || cfg->n_assets < 1 || cfg->n_assets > MGN_MAX_ASSETS) return 0;
-  return plan(cfg).total;
+  return mgn::arena_plan(*cfg).total;
 }
 
 int mgn_create(const mgn_config* cfg, const mgn_asset_source* sources, void* stream, void* arena,
@@ -478,7 +409,7 @@ int mgn_create(const mgn_config* cfg, const mgn_asset_source* sources, void* str
   e->apad = next_pow2(e->A);
   auto_layout(e);
   e->stream = (hipStream_t)stream;
-  const Offsets o = plan(cfg);
+  const mgn::ArenaPlan o = mgn::arena_plan(*cfg);
   e->arena_bytes = o.total;
   if (arena) {
     if (arena_bytes < o.total) {
@@ -495,37 +426,11 @@ int mgn_create(const mgn_config* cfg, const mgn_asset_source* sources, void* str
     }
     e->own_arena = true;
   }
-  char* b = (char*)e->arena;
-  mgn_views& v = e->v;
-  v.ledger = (double*)(b + o.L); v.mean_entry = (double*)(b + o.mep); v.borrowed = (double*)(b + o.Bm);
-  v.prices = (double*)(b + o.P); v.sine_x = (double*)(b + o.sx); v.ou_mean = (double*)(b + o.oum);
-  v.trend_dy = (double*)(b + o.dy); v.trend_len = (int32_t*)(b + o.tlen); v.trend_flags = (uint8_t*)(b + o.tfl);
-  v.cash = (double*)(b + o.cash); v.timestamp = (uint64_t*)(b + o.ts);
-  v.draw_skip = (uint64_t*)(b + o.dskip);
-  v.shaper_a = (double*)(b + o.sA); v.shaper_b = (double*)(b + o.sB);
-  v.ep_stats = (double*)(b + o.ep); v.episode_stats = (double*)(b + o.epstats);
-  v.ext_prices = (double*)(b + o.ext); v.units = (double*)(b + o.units); v.asset_idx = (int32_t*)(b + o.aidx);
-  v.ring = e->W ? (double*)(b + o.ring) : nullptr; v.ring_ts = e->W ? (uint64_t*)(b + o.ring_ts) : nullptr;
-  v.ring_head = (int32_t*)(b + o.rhead); v.ring_len = (int32_t*)(b + o.rlen);
-  v.win_price = e->W ? (double*)(b + o.wprice) : nullptr; v.win_port = e->W ? (double*)(b + o.wport) : nullptr;
-  v.win_ts = e->W ? (uint64_t*)(b + o.wts) : nullptr; v.reset_mask = (uint8_t*)(b + o.mask);
-  v.out.reward = (double*)(b + o.reward); v.out.agent_reward = (double*)(b + o.areward);
-  v.out.shaped = (double*)(b + o.shaped); v.out.done = (uint8_t*)(b + o.done);
-  v.out.obs_price = (double*)(b + o.obsp); v.out.obs_port = (double*)(b + o.obsport);
-  v.out.timestamp = (uint64_t*)(b + o.obsts); v.out.tprice = (double*)(b + o.tprice);
-  v.out.tunits = (double*)(b + o.tunits); v.out.tcost = (double*)(b + o.tcost);
-  v.out.risk = (uint8_t*)(b + o.risk); v.out.margin_call = (uint8_t*)(b + o.mcall);
-  v.out.n_shaped = (uint8_t*)(b + o.nshaped);
-  v.out.data_end = (uint8_t*)(b + o.dend);
-  v.replay_cursor = (int64_t*)(b + o.rcur);
-  v.aux = cfg->aux ? (double*)(b + o.aux) : nullptr;
-  v.nstep_ring = cfg->nstep > 1 ? (double*)(b + o.nring) : nullptr;
-  v.nstep_len = (int32_t*)(b + o.nlen); v.nstep_head = (int32_t*)(b + o.nhead);
-  v.n_envs = e->N; v.n_assets = e->A; v.window = e->W; v.reward_dim = e->D;
-  v.nstep = cfg->nstep; v.n_feats = e->F;
-  e->src_dev = (mgn_asset_source*)(b + o.src);
-  e->target_dev = (double*)(b + o.target);
-  e->disc_dev = (double*)(b + o.disc);
+  const mgn::Arena ar = mgn::arena_wire(*cfg, o, e->arena);
+  e->v = ar.v;
+  e->src_dev = ar.src;
+  e->target_dev = ar.target;
+  e->disc_dev = ar.disc;
   // discounts gamma^i = math.pow(gamma, i) (nstep_buffer.py:328), host libm pow
   double disc[2 * MGN_MAX_NSTEP];
   for (int i = 0; i < cfg->nstep; ++i) disc[i] = std::pow(cfg->discount, (double)i);
@@ -632,8 +537,28 @@ int mgn_step(mgn_env* e, int32_t kind, const double* units_dev, const int32_t* a
   return check_step(e, lst, "mgn_step");
 }
 
-static void time_mark(mgn_env* e, std::vector<hipEvent_t>& v, size_t& n, hipStream_t st);
-static bool time_pair(mgn_env* e, hipEvent_t& a, hipEvent_t& b);
+static void time_mark(mgn_env* e, std::vector<hipEvent_t>& v, size_t& n, hipStream_t st) {
+  if (!e->timing) return;
+  if (n == v.size()) {
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return;
+    v.push_back(ev);
+  }
+  (void)hipEventRecord(v[n++], st);
+}
+
+// mode 2: the next start / stop pair of the step pool, recorded by the launch
+static bool time_pair(mgn_env* e, hipEvent_t& a, hipEvent_t& b) {
+  while (e->t_step.size() < e->t_step_n + 2) {
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return false;
+    e->t_step.push_back(ev);
+  }
+  a = e->t_step[e->t_step_n];
+  b = e->t_step[e->t_step_n + 1];
+  e->t_step_n += 2;
+  return true;
+}
 
 int mgn_rollout(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, const mgn_traj* out) {
   if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
@@ -732,8 +657,6 @@ int mgn_window_clear(mgn_env* e, const uint8_t* mask_dev) {
   return check_hip(e, hipGetLastError(), "mgn_window_clear");
 }
 
-static void time_mark(mgn_env* e, std::vector<hipEvent_t>& v, size_t& n, hipStream_t st);
-
 int mgn_window(mgn_env* e, double* price_dev, double* port_dev, uint64_t* ts_dev) {
   if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
   if (e->W == 0) return fail(e, MGN_ERR_CONFIG, "handle has no window (window_length = 0)");
@@ -742,29 +665,6 @@ int mgn_window(mgn_env* e, double* price_dev, double* port_dev, uint64_t* ts_dev
                 port_dev ? port_dev : e->v.win_port, ts_dev ? ts_dev : e->v.win_ts, e->stream);
   time_mark(e, e->t_gather, e->t_gather_n, e->stream);
   return check_hip(e, hipGetLastError(), "mgn_window");
-}
-
-static void time_mark(mgn_env* e, std::vector<hipEvent_t>& v, size_t& n, hipStream_t st) {
-  if (!e->timing) return;
-  if (n == v.size()) {
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return;
-    v.push_back(ev);
-  }
-  (void)hipEventRecord(v[n++], st);
-}
-
-// mode 2: the next start / stop pair of the step pool, recorded by the launch
-static bool time_pair(mgn_env* e, hipEvent_t& a, hipEvent_t& b) {
-  while (e->t_step.size() < e->t_step_n + 2) {
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return false;
-    e->t_step.push_back(ev);
-  }
-  a = e->t_step[e->t_step_n];
-  b = e->t_step[e->t_step_n + 1];
-  e->t_step_n += 2;
-  return true;
 }
 
 static int grow(mgn_env* e, void** p, size_t bytes) {
@@ -1072,246 +972,6 @@ int mgn_feat_diff(const double* in_dev, double* out_dev, int64_t rows, int32_t c
   return check_hip(nullptr, hipGetLastError(), "mgn_feat_diff");
 }
 
-static int rnorm_ok(const mgn_rnorm* r) {
-  if (!r) return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser");
-  if (r->kind < MGN_RNORM_SHARPE_FW || r->kind > MGN_RNORM_SHARPE_EWMA)
-    return fail(nullptr, MGN_ERR_CONFIG, "unknown reward normaliser kind");
-  if (r->n_envs < 1) return fail(nullptr, MGN_ERR_CONFIG, "reward normaliser: n_envs must be >= 1");
-  // window 1: the reference's windowed stream divides by an emptied queue's
-  // size, its EWMA by w1 - w2 / w1 = 0
-  if (r->window < 2) return fail(nullptr, MGN_ERR_CONFIG, "reward normaliser: window must be >= 2");
-  if (!r->index || !r->est) return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser state");
-  if (r->kind == MGN_RNORM_SHARPE_EWMA) {
-    if (!r->zero_var || (r->table_len > 0 && !r->weights) || r->table_len < 0)
-      return fail(nullptr, MGN_ERR_CONFIG, "null SharpeEWMA weight table or zero-variance bytes");
-  } else if (!r->ring) {
-    return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser ring");
-  }
-  return MGN_OK;
-}
-
-int mgn_rnorm_reset(const mgn_rnorm* r, const uint8_t* mask_dev, void* stream) {
-  int rc = rnorm_ok(r);
-  if (rc != MGN_OK) return rc;
-  return check_hip(nullptr, (hipError_t)mgn::rnorm_launch_reset(*r, mask_dev, stream), "mgn_rnorm_reset");
-}
-
-int mgn_rnorm_stream(const mgn_rnorm* r, const double* reward_dev, const uint8_t* done_dev, double* out_dev,
-                     int32_t k_steps, void* stream) {
-  int rc = rnorm_ok(r);
-  if (rc != MGN_OK) return rc;
-  if (!reward_dev || !out_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: null reward or output");
-  if (k_steps < 1) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: k_steps must be >= 1");
-  return check_hip(nullptr, (hipError_t)mgn::rnorm_launch_stream(*r, reward_dev, done_dev, out_dev, k_steps, stream),
-                   "mgn_rnorm_stream");
-}
-
-static int tear_ok(const mgn_tear* t) {
-  if (!t) return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet");
-  if (t->n_envs < 1 || t->n_assets < 1 || t->max_steps < 1)
-    return fail(nullptr, MGN_ERR_CONFIG, "tearsheet: n_envs, n_assets and max_steps must be >= 1");
-  if (!t->ts || !t->equity || !t->prices) return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet series");
-  if (!t->len || !t->active || !t->sum_equity || !t->sum_reward || !t->sum_tcost || !t->peak || !t->valley ||
-      !t->pos_count || !t->overflow)
-    return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet state");
-  return MGN_OK;
-}
-
-int mgn_tear_reset(const mgn_tear* t, void* stream) {
-  int rc = tear_ok(t);
-  if (rc != MGN_OK) return rc;
-  return check_hip(nullptr, (hipError_t)mgn::tear_launch_reset(*t, stream), "mgn_tear_reset");
-}
-
-int mgn_tear_record(const mgn_tear* t, const int64_t* ts_dev, const double* equity_dev, const double* reward_dev,
-                    const double* prices_dev, const double* ledger_dev, const double* tcost_dev,
-                    const uint8_t* done_dev, void* stream) {
-  int rc = tear_ok(t);
-  if (rc != MGN_OK) return rc;
-  if (!ts_dev || !equity_dev || !reward_dev || !prices_dev || !ledger_dev || !tcost_dev || !done_dev)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_record: null step array");
-  return check_hip(nullptr,
-                   (hipError_t)mgn::tear_launch_record(*t, ts_dev, equity_dev, reward_dev, prices_dev, ledger_dev,
-                                                       tcost_dev, done_dev, stream),
-                   "mgn_tear_record");
-}
-
-int mgn_tear_summary(const mgn_tear* t, const int64_t* timeframes_dev, int32_t n_tf, double* out_dev, void* stream) {
-  int rc = tear_ok(t);
-  if (rc != MGN_OK) return rc;
-  if (n_tf < 0) return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: n_tf must be >= 0");
-  if (!out_dev || (n_tf > 0 && !timeframes_dev))
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: null timeframes or output");
-  // one lane per (asset, timeframe, env), 64 to a workgroup: the grid's x extent
-  if ((int64_t)t->n_envs * t->n_assets * (n_tf > 0 ? n_tf : 1) / 64 >= INT32_MAX)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: n_envs * n_assets * n_tf exceeds the launch grid");
-  return check_hip(nullptr, (hipError_t)mgn::tear_launch_summary(*t, timeframes_dev, n_tf, out_dev, stream),
-                   "mgn_tear_summary");
-}
-
-static int xbuf_ok(const mgn_xbuf* x) {
-  if (!x) return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer");
-  if (x->n_envs < 1 || x->n_assets < 1 || x->n_feats < 1)
-    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: n_envs, n_assets and n_feats must be >= 1");
-  if (x->window < 1) return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: window must be >= 1");
-  if (x->nstep < 1 || x->nstep > 255)
-    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: nstep must be 1..255 (n_shaped is a byte)");
-  if (x->reward_dim != 1 && x->reward_dim != x->n_assets)
-    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: reward_dim must be 1 or n_assets");
-  if (x->size < 1) return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: size must be >= 1");
-  if (!x->state_price || !x->state_port || !x->state_ts || !x->next_price || !x->next_port || !x->next_ts ||
-      !x->action || !x->reward || !x->done)
-    return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer storage");
-  if (!x->cursor || !x->pending) return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer cursor or pending counts");
-  return MGN_OK;
-}
-
-int mgn_xbuf_add(const mgn_xbuf* x, const double* hist_dev, const uint64_t* hist_ts_dev, const int32_t* hend_dev,
-                 const int32_t* hlen_dev, const int32_t* len0_dev, const int8_t* actions_dev, const uint8_t* done_dev,
-                 const double* shaped_dev, const uint8_t* n_shaped_dev, int32_t k_steps, void* stream) {
-  int rc = xbuf_ok(x);
-  if (rc != MGN_OK) return rc;
-  if (!hist_dev || !hist_ts_dev || !hend_dev || !hlen_dev || !len0_dev || !actions_dev || !done_dev || !shaped_dev ||
-      !n_shaped_dev)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: null launch array");
-  if (!x->carry_rows || !x->carry_ts || !x->carry_act || !x->carry_fill || !x->plan || !x->plan_base)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: null carry or plan arrays");
-  if (k_steps < 1 || k_steps > x->plan_steps)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: k_steps must be 1..plan_steps");
-  if (x->size < ((int64_t)k_steps + x->nstep - 1) * x->n_envs)
-    return fail(nullptr, MGN_ERR_CONFIG,
-                "mgn_xbuf_add: size must be >= (k_steps + nstep - 1) * n_envs (a launch must not overwrite its own slots)");
-  const int64_t hrows = (int64_t)x->window + (int64_t)k_steps * (x->window + 1);
-  if ((int64_t)k_steps * x->n_envs >= ((int64_t)1 << 31) || hrows >= ((int64_t)1 << 31))
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: launch exceeds 2^31 (step, env) pairs");
-  mgn::XbLaunch l;
-  l.hist = hist_dev; l.hist_ts = (const int64_t*)hist_ts_dev; l.hend = hend_dev; l.hlen = hlen_dev;
-  l.len0 = len0_dev; l.actions = actions_dev; l.done = done_dev; l.shaped = shaped_dev; l.n_shaped = n_shaped_dev;
-  l.K = k_steps; l.hrows = (int32_t)hrows;
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_add(*x, l, stream), "mgn_xbuf_add");
-}
-
-int mgn_xbuf_sample(const mgn_xbuf* x, const mgn_xbuf_batch* batch, int64_t n_batch, uint64_t seed, uint64_t call,
-                    void* stream) {
-  int rc = xbuf_ok(x);
-  if (rc != MGN_OK) return rc;
-  if (!batch) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_sample: null batch");
-  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_sample: n_batch must be 1..2^31-1");
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather(*x, nullptr, *batch, n_batch, seed, call, stream),
-                   "mgn_xbuf_sample");
-}
-
-int mgn_xbuf_gather(const mgn_xbuf* x, const int64_t* idx_dev, const mgn_xbuf_batch* batch, int64_t n_batch,
-                    void* stream) {
-  int rc = xbuf_ok(x);
-  if (rc != MGN_OK) return rc;
-  if (!batch || !idx_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather: null batch or indices");
-  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather: n_batch must be 1..2^31-1");
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather(*x, idx_dev, *batch, n_batch, 0, 0, stream),
-                   "mgn_xbuf_gather");
-}
-
-int mgn_xbuf_clear(const mgn_xbuf* x, int32_t nstep_only, void* stream) {
-  int rc = xbuf_ok(x);
-  if (rc != MGN_OK) return rc;
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_clear(*x, nstep_only, stream), "mgn_xbuf_clear");
-}
-
-static int wact_ok(const mgn_xbuf* x, const mgn_xbuf_wact* w) {
-  int rc = xbuf_ok(x);
-  if (rc != MGN_OK) return rc;
-  if (!w || !w->action || !w->carry) return fail(nullptr, MGN_ERR_CONFIG, "null weight-action store or carry");
-  return MGN_OK;
-}
-
-int mgn_xbuf_add_wact(const mgn_xbuf* x, const mgn_xbuf_wact* w, const double* weights_dev,
-                      const uint8_t* n_shaped_dev, int32_t k_steps, void* stream) {
-  int rc = wact_ok(x, w);
-  if (rc != MGN_OK) return rc;
-  if (!weights_dev || !n_shaped_dev || !x->plan || !x->plan_base)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: null weights, n_shaped or plan arrays");
-  if (k_steps < 1 || k_steps > x->plan_steps)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: k_steps must be 1..plan_steps");
-  if ((int64_t)k_steps * x->n_envs >= ((int64_t)1 << 31))
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: launch exceeds 2^31 (step, env) pairs");
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_add_wact(*x, *w, weights_dev, n_shaped_dev, k_steps, stream),
-                   "mgn_xbuf_add_wact");
-}
-
-int mgn_xbuf_gather_wact(const mgn_xbuf* x, const mgn_xbuf_wact* w, const int64_t* idx_dev, void* action_out,
-                         int64_t n_batch, void* stream) {
-  int rc = wact_ok(x, w);
-  if (rc != MGN_OK) return rc;
-  if (!idx_dev || !action_out) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather_wact: null indices or output");
-  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather_wact: n_batch must be 1..2^31-1");
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather_wact(*x, *w, idx_dev, action_out, n_batch, stream),
-                   "mgn_xbuf_gather_wact");
-}
-
-static int pbuf_ok(const mgn_xbuf* x, const mgn_pbuf* p) {
-  int rc = xbuf_ok(x);
-  if (rc != MGN_OK) return rc;
-  if (!p) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer");
-  if (p->tree_size != mgn::pb_tree_size(x->size))
-    return fail(nullptr, MGN_ERR_CONFIG, "prioritized buffer: tree_size must be the next power of two >= size");
-  if (!p->tree_sum || !p->tree_min) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer trees");
-  if (!p->cached_idx || !p->owner) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer index cache or scratch");
-  if (p->cached_cap < 1 || p->cached_cap >= ((int64_t)1 << 31) || p->cached_len < 0 || p->cached_len > p->cached_cap)
-    return fail(nullptr, MGN_ERR_CONFIG, "prioritized buffer: cached_cap must be 1..2^31-1 and cached_len within it");
-  return MGN_OK;
-}
-
-// prioritized_replay_buffer.py:52-55 (segment_tree.py:30-40)
-int mgn_pbuf_add(const mgn_xbuf* x, const mgn_pbuf* p, const uint8_t* n_shaped_dev, int32_t k_steps, double max_pa,
-                 int32_t seat, void* stream) {
-  int rc = pbuf_ok(x, p);
-  if (rc != MGN_OK) return rc;
-  if (!n_shaped_dev || !x->plan || !x->plan_base)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: null n_shaped or plan arrays");
-  if (k_steps < 1 || k_steps > x->plan_steps)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: k_steps must be 1..plan_steps");
-  if (max_pa != max_pa) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: max_pa is NaN");
-  if (seat != MGN_PBUF_SEAT_NEXT && seat != MGN_PBUF_SEAT_WRITTEN)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: seat must be MGN_PBUF_SEAT_NEXT or MGN_PBUF_SEAT_WRITTEN");
-  return check_hip(nullptr,
-                   (hipError_t)mgn::pbuf_launch_add(*x, *p, n_shaped_dev, k_steps, max_pa,
-                                                    seat == MGN_PBUF_SEAT_NEXT ? 1 : 0, stream),
-                   "mgn_pbuf_add");
-}
-
-// prioritized_replay_buffer.py:57-74 (segment_tree.py:14-28, :52-61)
-int mgn_pbuf_sample(const mgn_xbuf* x, mgn_pbuf* p, const mgn_xbuf_batch* batch, float* weights_dev, int64_t n_batch,
-                    double beta, uint64_t seed, uint64_t call, void* stream) {
-  int rc = pbuf_ok(x, p);
-  if (rc != MGN_OK) return rc;
-  if (!batch || !weights_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_sample: null batch or weights");
-  if (n_batch < 1 || n_batch > p->cached_cap)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_sample: n_batch must be 1..cached_cap");
-  rc = check_hip(nullptr, (hipError_t)mgn::pbuf_launch_draw(*x, *p, weights_dev, n_batch, beta, seed, call, stream),
-                 "mgn_pbuf_sample");
-  if (rc != MGN_OK) return rc;
-  p->cached_len = n_batch;
-  return check_hip(nullptr, (hipError_t)mgn::xbuf_launch_gather(*x, p->cached_idx, *batch, n_batch, 0, 0, stream),
-                   "mgn_pbuf_sample");
-}
-
-// prioritized_replay_buffer.py:76-83
-int mgn_pbuf_update(const mgn_xbuf* x, mgn_pbuf* p, const double* pa_dev, int64_t n_batch, void* stream) {
-  int rc = pbuf_ok(x, p);
-  if (rc != MGN_OK) return rc;
-  if (!pa_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: null priorities");
-  if (p->cached_len < 1)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: no cached batch (sample another batch before updating priorities)");
-  if (n_batch < 1 || n_batch != p->cached_len)
-    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: n_batch differs from the cached batch");
-  rc = check_hip(nullptr, (hipError_t)mgn::pbuf_launch_update(*x, *p, pa_dev, n_batch, stream), "mgn_pbuf_update");
-  if (rc == MGN_OK) p->cached_len = 0;
-  return rc;
-}
-
 int mgn_set_layout(mgn_env* e, int32_t assets_per_lane) {
   if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
   if (assets_per_lane == 0) {
@@ -1454,27 +1114,21 @@ int mgn_load_state(mgn_env* e, const void* src, size_t bytes) {
   // reverse, would leave e->replay and the restored table disagreeing)
   if ((h.replay != 0) != e->replay)
     return fail(e, MGN_ERR_CONFIG, "state blob of a replay handle loaded into a generator handle, or the reverse");
-  {
-    const mgn_asset_source* bs = reinterpret_cast<const mgn_asset_source*>(
-        static_cast<const char*>(src) + sizeof h + plan(&c).src);
-    for (int i = 0; i < e->A; ++i) {
-      int32_t k;
-      std::memcpy(&k, &bs[i].kind, sizeof k);
-      if (k != e->kinds[i] && k != MGN_SRC_EXTERNAL && e->kinds[i] != MGN_SRC_EXTERNAL)
-        return fail(e, MGN_ERR_CONFIG, "state blob's source kind differs from the handle's for asset " +
-                                           std::to_string(i));
-    }
+  const mgn_asset_source* bs = reinterpret_cast<const mgn_asset_source*>(
+      static_cast<const char*>(src) + sizeof h + mgn::arena_src_offset(mgn::arena_plan(c)));
+  for (int i = 0; i < e->A; ++i) {
+    int32_t k;
+    std::memcpy(&k, &bs[i].kind, sizeof k);
+    if (k != e->kinds[i] && k != MGN_SRC_EXTERNAL && e->kinds[i] != MGN_SRC_EXTERNAL)
+      return fail(e, MGN_ERR_CONFIG, "state blob's source kind differs from the handle's for asset " +
+                                         std::to_string(i));
   }
   int rc = check_hip(e, hipMemcpyAsync(e->arena, (const char*)src + sizeof h, e->arena_bytes,
                                        hipMemcpyHostToDevice, e->stream), "mgn_load_state");
   if (rc == MGN_OK) rc = check_hip(e, hipStreamSynchronize(e->stream), "mgn_load_state (sync)");
   if (rc != MGN_OK) return rc;
   e->cfg = c;
-  {
-    const mgn_asset_source* bs = reinterpret_cast<const mgn_asset_source*>(
-        static_cast<const char*>(src) + sizeof h + plan(&c).src);
-    for (int i = 0; i < e->A; ++i) std::memcpy(&e->kinds[i], &bs[i].kind, sizeof(int32_t));
-  }
+  for (int i = 0; i < e->A; ++i) std::memcpy(&e->kinds[i], &bs[i].kind, sizeof(int32_t));
   auto_layout(e);
   return MGN_OK;
 }

@@ -68,13 +68,7 @@ MGN_UNITS(MGN_X)
   void launch_init_a##A(int m, const InitArgs& a); \
   void launch_val_a##A(int m, const ValArgs& a);   \
   void launch_wtu_a##A(int m, const WtuArgs& a);
-MGN_DECLARE_APAD(1)
-MGN_DECLARE_APAD(2)
-MGN_DECLARE_APAD(4)
-MGN_DECLARE_APAD(8)
-MGN_DECLARE_APAD(16)
-MGN_DECLARE_APAD(32)
-MGN_DECLARE_APAD(64)
+MGN_APADS(MGN_DECLARE_APAD)
 #undef MGN_DECLARE_APAD
 
 }  // namespace mgn

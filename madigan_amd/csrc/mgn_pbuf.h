@@ -162,13 +162,6 @@ MGN_XB_HD int64_t pb_sample_index(const double* tree_sum, int64_t ts, double tot
   return idx >= 0 && idx < filled ? idx : -1;
 }
 
-// the launches of mgn_pbuf.hip (hipError_t as int), for mgn_api.hip
-int pbuf_launch_add(const mgn_xbuf& x, const mgn_pbuf& p, const uint8_t* n_shaped, int32_t K, double max_pa,
-                    int32_t off, void* stream);
-int pbuf_launch_draw(const mgn_xbuf& x, const mgn_pbuf& p, float* weights, int64_t n_batch, double beta,
-                     uint64_t seed, uint64_t call, void* stream);
-int pbuf_launch_update(const mgn_xbuf& x, const mgn_pbuf& p, const double* pa, int64_t n_batch, void* stream);
-
 }  // namespace mgn
 
 #endif  // MGN_PBUF_H_

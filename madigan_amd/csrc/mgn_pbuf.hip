@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mgn_pbuf.h"
+#include "mgn_status.h"
 
 namespace mgn {
 namespace {
@@ -154,30 +155,80 @@ __global__ __launch_bounds__(PB_UPDATE_BLOCK) void k_pbuf_update(mgn_xbuf x, mgn
   }
 }
 
+int pbuf_ok(const mgn_xbuf* x, const mgn_pbuf* p) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!p) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer");
+  if (p->tree_size != pb_tree_size(x->size))
+    return fail(nullptr, MGN_ERR_CONFIG, "prioritized buffer: tree_size must be the next power of two >= size");
+  if (!p->tree_sum || !p->tree_min) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer trees");
+  if (!p->cached_idx || !p->owner) return fail(nullptr, MGN_ERR_CONFIG, "null prioritized buffer index cache or scratch");
+  if (p->cached_cap < 1 || p->cached_cap >= ((int64_t)1 << 31) || p->cached_len < 0 || p->cached_len > p->cached_cap)
+    return fail(nullptr, MGN_ERR_CONFIG, "prioritized buffer: cached_cap must be 1..2^31-1 and cached_len within it");
+  return MGN_OK;
+}
+
 }  // namespace
-
-int pbuf_launch_add(const mgn_xbuf& x, const mgn_pbuf& p, const uint8_t* n_shaped, int32_t K, double max_pa,
-                    int32_t off, void* stream) {
-  const hipStream_t st = (hipStream_t)stream;
-  const int64_t bl = p.tree_size < PB_LEAVES ? p.tree_size : PB_LEAVES;
-  const int64_t blocks = (x.size - 1) / bl + 1;  // the blocks that hold a slot's leaf
-  hipLaunchKernelGGL(k_pbuf_add, dim3((unsigned)blocks), dim3(PB_ADD_BLOCK), 0, st, x, p, n_shaped, K, max_pa, off);
-  if (p.tree_size > PB_LEAVES)
-    hipLaunchKernelGGL(k_pbuf_add_top, dim3(1), dim3(PB_TOP_BLOCK), 0, st, x, p, n_shaped, K, off);
-  return (int)hipGetLastError();
-}
-
-int pbuf_launch_draw(const mgn_xbuf& x, const mgn_pbuf& p, float* weights, int64_t n_batch, double beta,
-                     uint64_t seed, uint64_t call, void* stream) {
-  const unsigned grid = (unsigned)((n_batch + PB_DRAW_BLOCK - 1) / PB_DRAW_BLOCK);
-  hipLaunchKernelGGL(k_pbuf_draw, dim3(grid), dim3(PB_DRAW_BLOCK), 0, (hipStream_t)stream, x, p, weights, n_batch,
-                     beta, seed, call);
-  return (int)hipGetLastError();
-}
-
-int pbuf_launch_update(const mgn_xbuf& x, const mgn_pbuf& p, const double* pa, int64_t n_batch, void* stream) {
-  hipLaunchKernelGGL(k_pbuf_update, dim3(1), dim3(PB_UPDATE_BLOCK), 0, (hipStream_t)stream, x, p, pa, n_batch);
-  return (int)hipGetLastError();
-}
-
 }  // namespace mgn
+
+using namespace mgn;
+
+extern "C" {
+
+// prioritized_replay_buffer.py:52-55 (segment_tree.py:30-40)
+int mgn_pbuf_add(const mgn_xbuf* x, const mgn_pbuf* p, const uint8_t* n_shaped_dev, int32_t k_steps, double max_pa,
+                 int32_t seat, void* stream) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!n_shaped_dev || !x->plan || !x->plan_base)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: null n_shaped or plan arrays");
+  if (k_steps < 1 || k_steps > x->plan_steps)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: k_steps must be 1..plan_steps");
+  if (max_pa != max_pa) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: max_pa is NaN");
+  if (seat != MGN_PBUF_SEAT_NEXT && seat != MGN_PBUF_SEAT_WRITTEN)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_add: seat must be MGN_PBUF_SEAT_NEXT or MGN_PBUF_SEAT_WRITTEN");
+  const hipStream_t st = (hipStream_t)stream;
+  const int32_t off = seat == MGN_PBUF_SEAT_NEXT ? 1 : 0;
+  const int64_t bl = p->tree_size < PB_LEAVES ? p->tree_size : PB_LEAVES;
+  const int64_t blocks = (x->size - 1) / bl + 1;  // the blocks that hold a slot's leaf
+  hipLaunchKernelGGL(k_pbuf_add, dim3((unsigned)blocks), dim3(PB_ADD_BLOCK), 0, st, *x, *p, n_shaped_dev, k_steps,
+                     max_pa, off);
+  if (p->tree_size > PB_LEAVES)
+    hipLaunchKernelGGL(k_pbuf_add_top, dim3(1), dim3(PB_TOP_BLOCK), 0, st, *x, *p, n_shaped_dev, k_steps, off);
+  return check_hip(nullptr, hipGetLastError(), "mgn_pbuf_add");
+}
+
+// prioritized_replay_buffer.py:57-74 (segment_tree.py:14-28, :52-61)
+int mgn_pbuf_sample(const mgn_xbuf* x, mgn_pbuf* p, const mgn_xbuf_batch* batch, float* weights_dev, int64_t n_batch,
+                    double beta, uint64_t seed, uint64_t call, void* stream) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!batch || !weights_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_sample: null batch or weights");
+  if (n_batch < 1 || n_batch > p->cached_cap)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_sample: n_batch must be 1..cached_cap");
+  const unsigned grid = (unsigned)((n_batch + PB_DRAW_BLOCK - 1) / PB_DRAW_BLOCK);
+  hipLaunchKernelGGL(k_pbuf_draw, dim3(grid), dim3(PB_DRAW_BLOCK), 0, (hipStream_t)stream, *x, *p, weights_dev,
+                     n_batch, beta, seed, call);
+  rc = check_hip(nullptr, hipGetLastError(), "mgn_pbuf_sample");
+  if (rc != MGN_OK) return rc;
+  p->cached_len = n_batch;
+  return check_hip(nullptr, (hipError_t)xbuf_launch_gather(*x, p->cached_idx, *batch, n_batch, 0, 0, stream),
+                   "mgn_pbuf_sample");
+}
+
+// prioritized_replay_buffer.py:76-83
+int mgn_pbuf_update(const mgn_xbuf* x, mgn_pbuf* p, const double* pa_dev, int64_t n_batch, void* stream) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!pa_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: null priorities");
+  if (p->cached_len < 1)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: no cached batch (sample another batch before updating priorities)");
+  if (n_batch < 1 || n_batch != p->cached_len)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_pbuf_update: n_batch differs from the cached batch");
+  hipLaunchKernelGGL(k_pbuf_update, dim3(1), dim3(PB_UPDATE_BLOCK), 0, (hipStream_t)stream, *x, *p, pa_dev, n_batch);
+  rc = check_hip(nullptr, hipGetLastError(), "mgn_pbuf_update");
+  if (rc == MGN_OK) p->cached_len = 0;
+  return rc;
+}
+
+}  // extern "C"

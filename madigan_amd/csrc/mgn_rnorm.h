@@ -185,11 +185,5 @@ MGN_RN_HD double rn_window_step(int32_t kind, RnState& s, double* ring, int64_t 
   }
 }
 
-// launchers of mgn_rnorm.hip (the descriptor is validated by the caller);
-// each returns the HIP status of its launch as an int
-int rnorm_launch_reset(const mgn_rnorm& r, const uint8_t* mask_dev, void* stream);
-int rnorm_launch_stream(const mgn_rnorm& r, const double* reward_dev, const uint8_t* done_dev, double* out_dev,
-                        int32_t k_steps, void* stream);
-
 }  // namespace mgn
 #endif

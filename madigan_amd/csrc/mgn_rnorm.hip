@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mgn_rnorm.h"
+#include "mgn_status.h"
 
 #if defined(MGN_RNORM_ENV_MAJOR) && !defined(MGN_DIAG)
 #error "MGN_RNORM_ENV_MAJOR is a measurement switch of diagnostic builds (tools/build_variant.py)"
@@ -166,41 +167,71 @@ __global__ __launch_bounds__(256) void k_rnorm_reset(mgn_rnorm r, const uint8_t*
   if (ewma) r.zero_var[e] = 0;
 }
 
-}  // namespace
-
-int rnorm_launch_reset(const mgn_rnorm& r, const uint8_t* mask_dev, void* stream) {
-  hipLaunchKernelGGL(k_rnorm_reset, dim3((unsigned)((r.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r,
-                     mask_dev);
-  return (int)hipGetLastError();
+// the descriptor of every mgn_rnorm_* entry point
+int rnorm_ok(const mgn_rnorm* r) {
+  if (!r) return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser");
+  if (r->kind < MGN_RNORM_SHARPE_FW || r->kind > MGN_RNORM_SHARPE_EWMA)
+    return fail(nullptr, MGN_ERR_CONFIG, "unknown reward normaliser kind");
+  if (r->n_envs < 1) return fail(nullptr, MGN_ERR_CONFIG, "reward normaliser: n_envs must be >= 1");
+  // window 1: the reference's windowed stream divides by an emptied queue's
+  // size, its EWMA by w1 - w2 / w1 = 0
+  if (r->window < 2) return fail(nullptr, MGN_ERR_CONFIG, "reward normaliser: window must be >= 2");
+  if (!r->index || !r->est) return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser state");
+  if (r->kind == MGN_RNORM_SHARPE_EWMA) {
+    if (!r->zero_var || (r->table_len > 0 && !r->weights) || r->table_len < 0)
+      return fail(nullptr, MGN_ERR_CONFIG, "null SharpeEWMA weight table or zero-variance bytes");
+  } else if (!r->ring) {
+    return fail(nullptr, MGN_ERR_CONFIG, "null reward normaliser ring");
+  }
+  return MGN_OK;
 }
 
-int rnorm_launch_stream(const mgn_rnorm& r, const double* reward_dev, const uint8_t* done_dev, double* out_dev,
-                        int32_t k_steps, void* stream) {
-  const dim3 grid((unsigned)((r.n_envs + RN_BLOCK - 1) / RN_BLOCK)), block(RN_BLOCK);
+}  // namespace
+}  // namespace mgn
+
+using namespace mgn;
+
+extern "C" {
+
+int mgn_rnorm_reset(const mgn_rnorm* r, const uint8_t* mask_dev, void* stream) {
+  int rc = rnorm_ok(r);
+  if (rc != MGN_OK) return rc;
+  hipLaunchKernelGGL(k_rnorm_reset, dim3((unsigned)((r->n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *r,
+                     mask_dev);
+  return check_hip(nullptr, hipGetLastError(), "mgn_rnorm_reset");
+}
+
+int mgn_rnorm_stream(const mgn_rnorm* r, const double* reward_dev, const uint8_t* done_dev, double* out_dev,
+                     int32_t k_steps, void* stream) {
+  int rc = rnorm_ok(r);
+  if (rc != MGN_OK) return rc;
+  if (!reward_dev || !out_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: null reward or output");
+  if (k_steps < 1) return fail(nullptr, MGN_ERR_CONFIG, "mgn_rnorm_stream: k_steps must be >= 1");
+  const dim3 grid((unsigned)((r->n_envs + RN_BLOCK - 1) / RN_BLOCK)), block(RN_BLOCK);
   const hipStream_t st = (hipStream_t)stream;
-  switch (r.kind) {
+  switch (r->kind) {
     case MGN_RNORM_SHARPE_FW:
-      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SHARPE_FW>, grid, block, 0, st, r, reward_dev, done_dev, out_dev,
+      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SHARPE_FW>, grid, block, 0, st, *r, reward_dev, done_dev, out_dev,
                          k_steps);
       break;
     case MGN_RNORM_SORTINO_FW_A:
-      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SORTINO_FW_A>, grid, block, 0, st, r, reward_dev, done_dev, out_dev,
+      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SORTINO_FW_A>, grid, block, 0, st, *r, reward_dev, done_dev, out_dev,
                          k_steps);
       break;
     case MGN_RNORM_SORTINO_FW_B:
-      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SORTINO_FW_B>, grid, block, 0, st, r, reward_dev, done_dev, out_dev,
+      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SORTINO_FW_B>, grid, block, 0, st, *r, reward_dev, done_dev, out_dev,
                          k_steps);
       break;
     case MGN_RNORM_SORTINO_FW_C:
-      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SORTINO_FW_C>, grid, block, 0, st, r, reward_dev, done_dev, out_dev,
+      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SORTINO_FW_C>, grid, block, 0, st, *r, reward_dev, done_dev, out_dev,
                          k_steps);
       break;
     default:
-      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SHARPE_EWMA>, grid, block, 0, st, r, reward_dev, done_dev, out_dev,
+      hipLaunchKernelGGL(k_rnorm_stream<MGN_RNORM_SHARPE_EWMA>, grid, block, 0, st, *r, reward_dev, done_dev, out_dev,
                          k_steps);
       break;
   }
-  return (int)hipGetLastError();
+  return check_hip(nullptr, hipGetLastError(), "mgn_rnorm_stream");
 }
 
-}  // namespace mgn
+}  // extern "C"

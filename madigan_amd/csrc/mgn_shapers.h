@@ -134,7 +134,7 @@ __device__ __forceinline__ double pop_term(int shaper, double r, double A, doubl
 // one position forward), so a pop costs O(1) instead of L summands and an
 // ordered sum.  The slides' rounding grows by 1/g per pop, so the sums are
 // re-formed from the buffer every n pops and the host grants this pop only
-// where g^n >= 1e-3 (mgn_api.hip kparams): drift <= n eps g^-n of the sums'
+// where g^n >= 1e-3 (mgn_api.hip nst_run_granted): drift <= n eps g^-n of the sums'
 // magnitude, < 1e-11 at n = 64.
 struct NstRun {
   double p1, pr, prr, n1, nr, nrr;

@@ -1,5 +1,5 @@
 // Test-episode tearsheet (madigan/utils/metrics.py:83-175 test_summary): the
-// per-row statements of the summary kernels (mgn_tear.hip) and their launchers.
+// per-row statements of the summary kernels (mgn_tear.hip).
 // Every operation is a correctly rounded IEEE binary64 one (the unit is built
 // with -ffp-contract=off and no fast-math), every sum one accumulator from
 // +0.0 in ascending time, and the logarithm is det_log, so a host restatement
@@ -57,15 +57,6 @@ struct TrWalk {
     return tl <= lim;
   }
 };
-
-// launchers of mgn_tear.hip (the descriptor and the arguments are validated by
-// the caller); each returns the HIP status of its launches as an int
-int tear_launch_reset(const mgn_tear& t, void* stream);
-int tear_launch_record(const mgn_tear& t, const int64_t* ts_dev, const double* equity_dev, const double* reward_dev,
-                       const double* prices_dev, const double* ledger_dev, const double* tcost_dev,
-                       const uint8_t* done_dev, void* stream);
-int tear_launch_summary(const mgn_tear& t, const int64_t* timeframes_dev, int32_t n_tf, double* out_dev,
-                        void* stream);
 
 }  // namespace mgn
 #endif

@@ -13,6 +13,7 @@
 // loads and vector stores only: no atomics, no LDS, no barriers, no scratch.
 #include <hip/hip_runtime.h>
 
+#include "mgn_status.h"
 #include "mgn_tear.h"
 
 namespace mgn {
@@ -222,34 +223,67 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tear_beta(mgn_tear t, const int64_
 
 inline dim3 tear_grid(int64_t lanes) { return dim3((unsigned)((lanes + TR_BLOCK - 1) / TR_BLOCK)); }
 
+// the descriptor of every mgn_tear_* entry point
+int tear_ok(const mgn_tear* t) {
+  if (!t) return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet");
+  if (t->n_envs < 1 || t->n_assets < 1 || t->max_steps < 1)
+    return fail(nullptr, MGN_ERR_CONFIG, "tearsheet: n_envs, n_assets and max_steps must be >= 1");
+  if (!t->ts || !t->equity || !t->prices) return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet series");
+  if (!t->len || !t->active || !t->sum_equity || !t->sum_reward || !t->sum_tcost || !t->peak || !t->valley ||
+      !t->pos_count || !t->overflow)
+    return fail(nullptr, MGN_ERR_CONFIG, "null tearsheet state");
+  return MGN_OK;
+}
+
 }  // namespace
-
-int tear_launch_reset(const mgn_tear& t, void* stream) {
-  hipLaunchKernelGGL(k_tear_reset, tear_grid(t.n_envs), dim3(TR_BLOCK), 0, (hipStream_t)stream, t);
-  return (int)hipGetLastError();
-}
-
-int tear_launch_record(const mgn_tear& t, const int64_t* ts_dev, const double* equity_dev, const double* reward_dev,
-                       const double* prices_dev, const double* ledger_dev, const double* tcost_dev,
-                       const uint8_t* done_dev, void* stream) {
-  hipLaunchKernelGGL(k_tear_record, tear_grid(t.n_envs), dim3(TR_BLOCK), 0, (hipStream_t)stream, t, ts_dev,
-                     equity_dev, reward_dev, prices_dev, ledger_dev, tcost_dev, done_dev);
-  return (int)hipGetLastError();
-}
-
-int tear_launch_summary(const mgn_tear& t, const int64_t* timeframes_dev, int32_t n_tf, double* out_dev,
-                        void* stream) {
-  const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_tear_scalars, tear_grid(t.n_envs), dim3(TR_BLOCK), 0, st, t, out_dev);
-  int rc = (int)hipGetLastError();
-  if (rc != 0 || n_tf == 0) return rc;
-  const int64_t lanes = (int64_t)t.n_envs * n_tf;
-  hipLaunchKernelGGL(k_tear_returns, tear_grid(lanes), dim3(TR_BLOCK), 0, st, t, timeframes_dev, n_tf, out_dev);
-  rc = (int)hipGetLastError();
-  if (rc != 0) return rc;
-  hipLaunchKernelGGL(k_tear_beta, tear_grid(lanes * t.n_assets), dim3(TR_BLOCK), 0, st, t, timeframes_dev, n_tf,
-                     out_dev);
-  return (int)hipGetLastError();
-}
-
 }  // namespace mgn
+
+using namespace mgn;
+
+extern "C" {
+
+int mgn_tear_reset(const mgn_tear* t, void* stream) {
+  int rc = tear_ok(t);
+  if (rc != MGN_OK) return rc;
+  hipLaunchKernelGGL(k_tear_reset, tear_grid(t->n_envs), dim3(TR_BLOCK), 0, (hipStream_t)stream, *t);
+  return check_hip(nullptr, hipGetLastError(), "mgn_tear_reset");
+}
+
+int mgn_tear_record(const mgn_tear* t, const int64_t* ts_dev, const double* equity_dev, const double* reward_dev,
+                    const double* prices_dev, const double* ledger_dev, const double* tcost_dev,
+                    const uint8_t* done_dev, void* stream) {
+  int rc = tear_ok(t);
+  if (rc != MGN_OK) return rc;
+  if (!ts_dev || !equity_dev || !reward_dev || !prices_dev || !ledger_dev || !tcost_dev || !done_dev)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_record: null step array");
+  hipLaunchKernelGGL(k_tear_record, tear_grid(t->n_envs), dim3(TR_BLOCK), 0, (hipStream_t)stream, *t, ts_dev,
+                     equity_dev, reward_dev, prices_dev, ledger_dev, tcost_dev, done_dev);
+  return check_hip(nullptr, hipGetLastError(), "mgn_tear_record");
+}
+
+int mgn_tear_summary(const mgn_tear* t, const int64_t* timeframes_dev, int32_t n_tf, double* out_dev, void* stream) {
+  int rc = tear_ok(t);
+  if (rc != MGN_OK) return rc;
+  if (n_tf < 0) return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: n_tf must be >= 0");
+  if (!out_dev || (n_tf > 0 && !timeframes_dev))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: null timeframes or output");
+  // one lane per (asset, timeframe, env), 64 to a workgroup: the grid's x extent
+  if ((int64_t)t->n_envs * t->n_assets * (n_tf > 0 ? n_tf : 1) / 64 >= INT32_MAX)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_tear_summary: n_envs * n_assets * n_tf exceeds the launch grid");
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_tear_scalars, tear_grid(t->n_envs), dim3(TR_BLOCK), 0, st, *t, out_dev);
+  hipError_t h = hipGetLastError();
+  if (h == hipSuccess && n_tf > 0) {
+    const int64_t lanes = (int64_t)t->n_envs * n_tf;
+    hipLaunchKernelGGL(k_tear_returns, tear_grid(lanes), dim3(TR_BLOCK), 0, st, *t, timeframes_dev, n_tf, out_dev);
+    h = hipGetLastError();
+    if (h == hipSuccess) {
+      hipLaunchKernelGGL(k_tear_beta, tear_grid(lanes * t->n_assets), dim3(TR_BLOCK), 0, st, *t, timeframes_dev, n_tf,
+                         out_dev);
+      h = hipGetLastError();
+    }
+  }
+  return check_hip(nullptr, h, "mgn_tear_summary");
+}
+
+}  // extern "C"

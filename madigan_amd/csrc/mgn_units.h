@@ -249,6 +249,9 @@ using Unit_a64w = UnitWts<64>;
   X(a1) X(a2) X(a4) X(a8) X(a16) X(a32) X(a64) X(a1t) X(a1tnst) X(a2nst) X(a4nst) X(a8nst) X(a16nst) X(a8t) \
   X(a8k1) X(a8k1w) X(a16m2) X(a1w) X(a2w) X(a4w) X(a8w) X(a16w) X(a32w) X(a64w)
 
+// the padded asset counts, in the order of apad_unit
+#define MGN_APADS(X) X(1) X(2) X(4) X(8) X(16) X(32) X(64)
+
 // the unit instantiates the chosen kernel
 template <class U>
 constexpr bool unit_owns(const StepChoice& c) {

@@ -167,17 +167,13 @@ struct XbLaunch {
   int32_t K, hrows;
 };
 
-// the launches of mgn_xbuf.hip (hipError_t as int), for mgn_api.hip
-int xbuf_launch_add(const mgn_xbuf& x, const XbLaunch& l, void* stream);
+// mgn_xbuf.hip, shared with mgn_pbuf.hip: the validated descriptor (MGN_OK, or
+// the refusal's status with its message recorded), and the batch gather behind
+// mgn_xbuf_sample (idx_dev null: Philox indices), mgn_xbuf_gather and
+// mgn_pbuf_sample; it returns the launch's HIP status (hipError_t as int)
+int xbuf_ok(const mgn_xbuf* x);
 int xbuf_launch_gather(const mgn_xbuf& x, const int64_t* idx_dev, const mgn_xbuf_batch& b, int64_t n_batch,
                        uint64_t seed, uint64_t call, void* stream);
-int xbuf_launch_clear(const mgn_xbuf& x, int32_t nstep_only, void* stream);
-// portfolio-weight actions: after xbuf_launch_add on the same stream / by the
-// indices of a gather
-int xbuf_launch_add_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const double* weights, const uint8_t* n_shaped,
-                         int32_t K, void* stream);
-int xbuf_launch_gather_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const int64_t* idx_dev, void* out,
-                            int64_t n_batch, void* stream);
 
 }  // namespace mgn
 

@@ -18,6 +18,7 @@
 // scan's partial sums, no scratch.
 #include <hip/hip_runtime.h>
 
+#include "mgn_status.h"
 #include "mgn_xbuf.h"
 
 namespace mgn {
@@ -373,53 +374,122 @@ __global__ __launch_bounds__(256) void k_xbuf_wact_gather(mgn_xbuf x, mgn_xbuf_w
   out[i] = (idx >= 0 && idx < filled) ? ((const T*)wa.action)[idx * P + c] : (T)0;
 }
 
+int wact_ok(const mgn_xbuf* x, const mgn_xbuf_wact* w) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!w || !w->action || !w->carry) return fail(nullptr, MGN_ERR_CONFIG, "null weight-action store or carry");
+  return MGN_OK;
+}
+
 }  // namespace
 
-int xbuf_launch_add_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const double* weights, const uint8_t* n_shaped,
-                         int32_t K, void* stream) {
-  const hipStream_t st = (hipStream_t)stream;
-  const int64_t P = x.n_assets + 1;
-  const dim3 grid((unsigned)(((int64_t)K * x.n_envs * P + 255) / 256)), cgrid((unsigned)((x.n_envs * P + 255) / 256));
-  if (wa.f32) {
-    hipLaunchKernelGGL(k_xbuf_wact_copy<float>, grid, dim3(256), 0, st, x, wa, weights, n_shaped, K);
-    if (x.nstep > 1) hipLaunchKernelGGL(k_xbuf_wact_carry<float>, cgrid, dim3(256), 0, st, x, wa, weights, K);
-  } else {
-    hipLaunchKernelGGL(k_xbuf_wact_copy<double>, grid, dim3(256), 0, st, x, wa, weights, n_shaped, K);
-    if (x.nstep > 1) hipLaunchKernelGGL(k_xbuf_wact_carry<double>, cgrid, dim3(256), 0, st, x, wa, weights, K);
-  }
-  return (int)hipGetLastError();
+int xbuf_ok(const mgn_xbuf* x) {
+  if (!x) return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer");
+  if (x->n_envs < 1 || x->n_assets < 1 || x->n_feats < 1)
+    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: n_envs, n_assets and n_feats must be >= 1");
+  if (x->window < 1) return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: window must be >= 1");
+  if (x->nstep < 1 || x->nstep > 255)
+    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: nstep must be 1..255 (n_shaped is a byte)");
+  if (x->reward_dim != 1 && x->reward_dim != x->n_assets)
+    return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: reward_dim must be 1 or n_assets");
+  if (x->size < 1) return fail(nullptr, MGN_ERR_CONFIG, "replay buffer: size must be >= 1");
+  if (!x->state_price || !x->state_port || !x->state_ts || !x->next_price || !x->next_port || !x->next_ts ||
+      !x->action || !x->reward || !x->done)
+    return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer storage");
+  if (!x->cursor || !x->pending) return fail(nullptr, MGN_ERR_CONFIG, "null replay buffer cursor or pending counts");
+  return MGN_OK;
 }
 
-int xbuf_launch_gather_wact(const mgn_xbuf& x, const mgn_xbuf_wact& wa, const int64_t* idx_dev, void* out,
-                            int64_t n_batch, void* stream) {
-  const dim3 grid((unsigned)((n_batch * (x.n_assets + 1) + 255) / 256));
-  if (wa.f32) {
-    hipLaunchKernelGGL(k_xbuf_wact_gather<float>, grid, dim3(256), 0, (hipStream_t)stream, x, wa, idx_dev, (float*)out,
-                       n_batch);
+}  // namespace mgn
+
+using namespace mgn;
+
+extern "C" {
+
+// portfolio-weight actions: after mgn_xbuf_add on the same stream
+int mgn_xbuf_add_wact(const mgn_xbuf* x, const mgn_xbuf_wact* w, const double* weights_dev,
+                      const uint8_t* n_shaped_dev, int32_t k_steps, void* stream) {
+  int rc = wact_ok(x, w);
+  if (rc != MGN_OK) return rc;
+  if (!weights_dev || !n_shaped_dev || !x->plan || !x->plan_base)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: null weights, n_shaped or plan arrays");
+  if (k_steps < 1 || k_steps > x->plan_steps)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: k_steps must be 1..plan_steps");
+  if ((int64_t)k_steps * x->n_envs >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add_wact: launch exceeds 2^31 (step, env) pairs");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t P = x->n_assets + 1;
+  const dim3 grid((unsigned)(((int64_t)k_steps * x->n_envs * P + 255) / 256)),
+      cgrid((unsigned)((x->n_envs * P + 255) / 256));
+  if (w->f32) {
+    hipLaunchKernelGGL(k_xbuf_wact_copy<float>, grid, dim3(256), 0, st, *x, *w, weights_dev, n_shaped_dev, k_steps);
+    if (x->nstep > 1) hipLaunchKernelGGL(k_xbuf_wact_carry<float>, cgrid, dim3(256), 0, st, *x, *w, weights_dev, k_steps);
   } else {
-    hipLaunchKernelGGL(k_xbuf_wact_gather<double>, grid, dim3(256), 0, (hipStream_t)stream, x, wa, idx_dev,
-                       (double*)out, n_batch);
+    hipLaunchKernelGGL(k_xbuf_wact_copy<double>, grid, dim3(256), 0, st, *x, *w, weights_dev, n_shaped_dev, k_steps);
+    if (x->nstep > 1) hipLaunchKernelGGL(k_xbuf_wact_carry<double>, cgrid, dim3(256), 0, st, *x, *w, weights_dev, k_steps);
   }
-  return (int)hipGetLastError();
+  return check_hip(nullptr, hipGetLastError(), "mgn_xbuf_add_wact");
 }
 
-int xbuf_launch_add(const mgn_xbuf& x, const XbLaunch& l, void* stream) {
+// by the indices of a gather
+int mgn_xbuf_gather_wact(const mgn_xbuf* x, const mgn_xbuf_wact* w, const int64_t* idx_dev, void* action_out,
+                         int64_t n_batch, void* stream) {
+  int rc = wact_ok(x, w);
+  if (rc != MGN_OK) return rc;
+  if (!idx_dev || !action_out) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather_wact: null indices or output");
+  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather_wact: n_batch must be 1..2^31-1");
+  const dim3 grid((unsigned)((n_batch * (x->n_assets + 1) + 255) / 256));
+  if (w->f32) {
+    hipLaunchKernelGGL(k_xbuf_wact_gather<float>, grid, dim3(256), 0, (hipStream_t)stream, *x, *w, idx_dev,
+                       (float*)action_out, n_batch);
+  } else {
+    hipLaunchKernelGGL(k_xbuf_wact_gather<double>, grid, dim3(256), 0, (hipStream_t)stream, *x, *w, idx_dev,
+                       (double*)action_out, n_batch);
+  }
+  return check_hip(nullptr, hipGetLastError(), "mgn_xbuf_gather_wact");
+}
+
+int mgn_xbuf_add(const mgn_xbuf* x, const double* hist_dev, const uint64_t* hist_ts_dev, const int32_t* hend_dev,
+                 const int32_t* hlen_dev, const int32_t* len0_dev, const int8_t* actions_dev, const uint8_t* done_dev,
+                 const double* shaped_dev, const uint8_t* n_shaped_dev, int32_t k_steps, void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!hist_dev || !hist_ts_dev || !hend_dev || !hlen_dev || !len0_dev || !actions_dev || !done_dev || !shaped_dev ||
+      !n_shaped_dev)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: null launch array");
+  if (!x->carry_rows || !x->carry_ts || !x->carry_act || !x->carry_fill || !x->plan || !x->plan_base)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: null carry or plan arrays");
+  if (k_steps < 1 || k_steps > x->plan_steps)
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: k_steps must be 1..plan_steps");
+  if (x->size < ((int64_t)k_steps + x->nstep - 1) * x->n_envs)
+    return fail(nullptr, MGN_ERR_CONFIG,
+                "mgn_xbuf_add: size must be >= (k_steps + nstep - 1) * n_envs (a launch must not overwrite its own slots)");
+  const int64_t hrows = (int64_t)x->window + (int64_t)k_steps * (x->window + 1);
+  if ((int64_t)k_steps * x->n_envs >= ((int64_t)1 << 31) || hrows >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_add: launch exceeds 2^31 (step, env) pairs");
+  XbLaunch l;
+  l.hist = hist_dev; l.hist_ts = (const int64_t*)hist_ts_dev; l.hend = hend_dev; l.hlen = hlen_dev;
+  l.len0 = len0_dev; l.actions = actions_dev; l.done = done_dev; l.shaped = shaped_dev; l.n_shaped = n_shaped_dev;
+  l.K = k_steps; l.hrows = (int32_t)hrows;
   const hipStream_t st = (hipStream_t)stream;
-  const unsigned envs = (unsigned)((x.n_envs + 255) / 256);
-  hipLaunchKernelGGL(k_xbuf_plan, dim3(envs), dim3(256), 0, st, x, l);
-  hipLaunchKernelGGL(k_xbuf_scan, dim3(1), dim3(XB_SCAN), 0, st, x, l);
-  const int64_t groups = ((int64_t)l.K * x.n_envs + XB_COPY_BLOCK / XB_BLOCK - 1) / (XB_COPY_BLOCK / XB_BLOCK);
+  const unsigned envs = (unsigned)((x->n_envs + 255) / 256);
+  hipLaunchKernelGGL(k_xbuf_plan, dim3(envs), dim3(256), 0, st, *x, l);
+  hipLaunchKernelGGL(k_xbuf_scan, dim3(1), dim3(XB_SCAN), 0, st, *x, l);
+  const int64_t groups = ((int64_t)l.K * x->n_envs + XB_COPY_BLOCK / XB_BLOCK - 1) / (XB_COPY_BLOCK / XB_BLOCK);
   const dim3 grid((unsigned)groups);
-  if (x.state_f32) {
-    hipLaunchKernelGGL(k_xbuf_copy<float>, grid, dim3(XB_COPY_BLOCK), 0, st, x, l);
+  if (x->state_f32) {
+    hipLaunchKernelGGL(k_xbuf_copy<float>, grid, dim3(XB_COPY_BLOCK), 0, st, *x, l);
   } else {
-    hipLaunchKernelGGL(k_xbuf_copy<double>, grid, dim3(XB_COPY_BLOCK), 0, st, x, l);
+    hipLaunchKernelGGL(k_xbuf_copy<double>, grid, dim3(XB_COPY_BLOCK), 0, st, *x, l);
   }
-  if (x.nstep > 1) hipLaunchKernelGGL(k_xbuf_carry, dim3(envs), dim3(256), 0, st, x, l);
-  return (int)hipGetLastError();
+  if (x->nstep > 1) hipLaunchKernelGGL(k_xbuf_carry, dim3(envs), dim3(256), 0, st, *x, l);
+  return check_hip(nullptr, hipGetLastError(), "mgn_xbuf_add");
 }
 
-int xbuf_launch_gather(const mgn_xbuf& x, const int64_t* idx_dev, const mgn_xbuf_batch& b, int64_t n_batch,
+}  // extern "C"
+
+int mgn::xbuf_launch_gather(const mgn_xbuf& x, const int64_t* idx_dev, const mgn_xbuf_batch& b, int64_t n_batch,
                        uint64_t seed, uint64_t call, void* stream) {
   const dim3 grid((unsigned)n_batch);
   if (x.state_f32) {
@@ -430,10 +500,36 @@ int xbuf_launch_gather(const mgn_xbuf& x, const int64_t* idx_dev, const mgn_xbuf
   return (int)hipGetLastError();
 }
 
-int xbuf_launch_clear(const mgn_xbuf& x, int32_t nstep_only, void* stream) {
-  hipLaunchKernelGGL(k_xbuf_clear, dim3((unsigned)((x.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     nstep_only);
-  return (int)hipGetLastError();
+extern "C" {
+
+int mgn_xbuf_sample(const mgn_xbuf* x, const mgn_xbuf_batch* batch, int64_t n_batch, uint64_t seed, uint64_t call,
+                    void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!batch) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_sample: null batch");
+  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_sample: n_batch must be 1..2^31-1");
+  return check_hip(nullptr, (hipError_t)xbuf_launch_gather(*x, nullptr, *batch, n_batch, seed, call, stream),
+                   "mgn_xbuf_sample");
 }
 
-}  // namespace mgn
+int mgn_xbuf_gather(const mgn_xbuf* x, const int64_t* idx_dev, const mgn_xbuf_batch* batch, int64_t n_batch,
+                    void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  if (!batch || !idx_dev) return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather: null batch or indices");
+  if (n_batch < 1 || n_batch >= ((int64_t)1 << 31))
+    return fail(nullptr, MGN_ERR_CONFIG, "mgn_xbuf_gather: n_batch must be 1..2^31-1");
+  return check_hip(nullptr, (hipError_t)xbuf_launch_gather(*x, idx_dev, *batch, n_batch, 0, 0, stream),
+                   "mgn_xbuf_gather");
+}
+
+int mgn_xbuf_clear(const mgn_xbuf* x, int32_t nstep_only, void* stream) {
+  int rc = xbuf_ok(x);
+  if (rc != MGN_OK) return rc;
+  hipLaunchKernelGGL(k_xbuf_clear, dim3((unsigned)((x->n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *x,
+                     nstep_only);
+  return check_hip(nullptr, hipGetLastError(), "mgn_xbuf_clear");
+}
+
+}  // extern "C"

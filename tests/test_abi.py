@@ -73,23 +73,53 @@ int main(void) {
 """
 
 
-def test_struct_layouts_match_ctypes(tmp_path):
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
+# every ctypes structure of _lib.py that mirrors one of the header's
+STRUCTS = {"mgn_config": L.Config, "mgn_traj": L.Traj, "mgn_views": L.Views,
+           "mgn_asset_source": L.AssetSource, "mgn_ring": L.Ring, "mgn_replay_tape": L.ReplayTape,
+           "mgn_hist_view": L.HistView, "mgn_rnorm": L.RNorm, "mgn_tear": L.Tear, "mgn_xbuf": L.XBuf,
+           "mgn_xbuf_batch": L.XBufBatch, "mgn_xbuf_wact": L.XBufWact, "mgn_pbuf": L.PBuf}
+
+
+def _compile_and_run(tmp_path, name, text):
+    src = tmp_path / (name + ".c")
+    src.write_text(text)
+    exe = tmp_path / name
     subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
                    check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True,
-                                                        check=True).stdout.splitlines())
-    py = {"mgn_config": L.Config, "mgn_traj": L.Traj, "mgn_views": L.Views,
-          "mgn_asset_source": L.AssetSource, "mgn_ring": L.Ring, "mgn_replay_tape": L.ReplayTape,
-          "mgn_hist_view": L.HistView}
+    return subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
+
+
+def test_struct_layouts_match_ctypes(tmp_path):
+    got = dict(line.split() for line in _compile_and_run(tmp_path, "layout", LAYOUT_C))
+    assert len(got) == 7 + 22
     for k, v in got.items():
         if "." in k:
             t, f = k.split(".")
-            assert getattr(py[t], f).offset == int(v), k
+            assert getattr(STRUCTS[t], f).offset == int(v), k
         else:
-            assert C.sizeof(py[k]) == int(v), k
+            assert C.sizeof(STRUCTS[k]) == int(v), k
+    # every field of every structure, from the ctypes _fields_ themselves: its
+    # offset and size in C, and no structure of _lib.py left out
+    mirrors = {v for v in vars(L).values() if isinstance(v, type) and issubclass(v, C.Structure)
+               and v is not C.Structure and not v.__name__.startswith("_")}
+    assert mirrors == set(STRUCTS.values())
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "madigan_amd.h"', "int main(void) {"]
+    for cname, cls in STRUCTS.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        for f, _ in cls._fields_:
+            lines.append(f'  printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname} *)0)->{f}));')
+    lines += ["  return 0;", "}", ""]
+    seen = 0
+    for line in _compile_and_run(tmp_path, "fields", "\n".join(lines)):
+        k, *v = line.split()
+        if "." in k:
+            t, f = k.split(".")
+            d = getattr(STRUCTS[t], f)
+            assert (d.offset, d.size) == (int(v[0]), int(v[1])), k
+            seen += 1
+        else:
+            assert C.sizeof(STRUCTS[k]) == int(v[0]), k
+    assert seen == sum(len(c._fields_) for c in STRUCTS.values())
 
 
 def test_arena_bytes_scales():

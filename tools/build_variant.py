@@ -28,7 +28,10 @@ def main():
     # the translation units rebuilt with the extra flags (MGN_VARIANT_UNITS,
     # comma-separated unit suffixes: default 8t, the C3 headline's unit)
     units = os.environ.get("MGN_VARIANT_UNITS", "8t").split(",")
-    # (an entry ending in .hip names a unit outright, e.g. mgn_rnorm.hip)
+    # (an entry ending in .hip names a unit outright, e.g. mgn_rnorm.hip.
+    # mgn_set_ablation and the MGN_NO_GK switch are mgn_api.hip's; the
+    # descriptor entry points in mgn_rnorm / tear / xbuf / pbuf.hip read no
+    # MGN_DIAG switch on the host side)
     redo = {"mgn_api.hip"} | {u if u.endswith(".hip") else f"mgn_launch_a{u}.hip" for u in units}
 
     def one(src):
