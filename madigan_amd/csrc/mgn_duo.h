@@ -38,6 +38,7 @@
 #include "mgn_broker.h"
 #include "mgn_consts.h"
 #include "mgn_diag.h"
+#include "mgn_finish.h"
 #include "mgn_gout.h"
 #include "mgn_lane.h"
 #include "mgn_math.h"
@@ -87,8 +88,9 @@ struct DuoShared {
 // n = 1 shaping) right after the step's post-tick sums and publish it in the
 // step record; the generator lanes store the record's outputs one iteration
 // later (duo_store) and keep the episode statistics and the window ring
-// (preprocessor.py:172-175).  Each value is the same expression
-// of the same operands as in k_step, so every output stays bit-identical.
+// (preprocessor.py:172-175).  Each statement is the one k_step
+// evaluates (the functions of mgn_finish.h and mgn_shapers.h), so every
+// output stays bit-identical.
 struct GenOut {
   double ep_ret, ep_len, n_done;
   int32_t head, len;
@@ -109,24 +111,12 @@ __device__ __forceinline__ void ledger_finish(DuoRec<S>& rc, const Lane<1>& s, c
   const double Lc = s.L[0], P = s.P[0];
   double ar[M];
   ar[0] = 0.;
-  if (valid && need_ar) {
-    double v = (((Lc * P) - prevVal) - (tu * tp + tc)) / prevEq;
-    v += 1;
-    v = (v < .35) ? .35 : v;
-    ar[0] = log_ratio(v);
-  }
+  if (valid && need_ar) ar[0] = agent_reward(Lc, P, prevVal, tu, tp, tc, prevEq);
   double cos_term = 0.;
   if (p.shaper == MGN_SHAPER_PPC) {
     const double port0 = (cash - qb) / curEq;
-    const double portA = (Lc * P) / curEq;
-    double pp[M], pq[M];
-    const double qv = valid ? s_tgt[1 + s.asset[0]] : 0.;
-    const double pv = valid ? portA : 0.;
-    pp[0] = pv * pv;
-    pq[0] = pv * qv;
-    const double np_ = sqrt(port0 * port0 + canon<M, S>(pp));
-    const double dot = port0 * s_tgt[0] + canon<M, S>(pq);
-    cos_term = p.cos_temp * (dot / (np_ * g.cos_qn));
+    const double portA[M] = {(Lc * P) / curEq};
+    cos_term = ppc_cos<M, S>(s.valid, s.asset, port0, portA, s_tgt, p.cos_temp, g.cos_qn);
   }
   double shaped_s = 0., rin_s = 0., shaped_v = 0.;
   if constexpr (NST) {
@@ -134,16 +124,7 @@ __device__ __forceinline__ void ledger_finish(DuoRec<S>& rc, const Lane<1>& s, c
     if (D == 1) rin_s = (p.reward_mode == MGN_REWARD_AGENT_SUM) ? canon<M, S>(ar) : reward;
   } else if (D == 1) {
     rin_s = (p.reward_mode == MGN_REWARD_AGENT_SUM) ? canon<M, S>(ar) : reward;
-    if (p.shaper == MGN_SHAPER_DDR) {  // shape() for DDR (nstep_buffer.py:128-162)
-      const double r = rin_s;
-      shaped_s = clip1((0.0 + 1.0 * ddr_one_pre(r, g.shA, g.shB, ddr_pre(g.shA, g.shB))) / 1);
-      double m = r < 0. ? r : 0.;
-      if (r != r) m = r;
-      g.shA += p.eta * (r - g.shA);
-      g.shB += p.eta * (m * m - g.shB);
-    } else {
-      shaped_s = shape(p.shaper, rin_s, g.shA, g.shB, p.eta, cos_term, p.sexp);
-    }
+    shaped_s = shape_one(p.shaper, rin_s, g.shA, g.shB, p.eta, cos_term, p.sexp);
   } else {
     shaped_v = valid ? shape(p.shaper, ar[0], g.shA, g.shB, p.eta, cos_term, p.sexp) : 0.;
   }
@@ -245,7 +226,7 @@ __device__ __forceinline__ void duo_store(const DuoRec<S>& sh, const Lane<1>& s,
       // if full, every entry on done; the popped aggregates are row k's
       const int n = p.nstep;
       const int L1 = ns.len + 1;
-      const int pops = done ? L1 : (L1 >= n ? 1 : 0);
+      const int pops = pop_count(done, L1, n);
       const bool ppc = p.shaper == MGN_SHAPER_PPC;
       const double cosv = sh.rCos[el];
       MGN_G double* row = (om & O_SHP) ? out.shaped + (oN + env) * (size_t)n * D : nullptr;
@@ -274,15 +255,7 @@ __device__ __forceinline__ void duo_store(const DuoRec<S>& sh, const Lane<1>& s,
           double res = acc;
           if (p.shaper == MGN_SHAPER_DSR || p.shaper == MGN_SHAPER_DDR) {
             res = clip1(acc / L1);
-            const double r0 = ns.ring[ns.head];
-            ns.A += p.eta * (r0 - ns.A);
-            if (p.shaper == MGN_SHAPER_DSR) {
-              ns.B += p.eta * (r0 * r0 - ns.B);
-            } else {
-              double m = r0 < 0. ? r0 : 0.;
-              if (r0 != r0) m = r0;
-              ns.B += p.eta * (m * m - ns.B);
-            }
+            est_update(p.shaper, ns.ring[ns.head], ns.A, ns.B, p.eta);
           }
           if (row) ost(row, res);
         }
@@ -302,20 +275,7 @@ __device__ __forceinline__ void duo_store(const DuoRec<S>& sh, const Lane<1>& s,
       ns.head = (ns.head + pops) % n;
       ns.len = L1 - pops;
     }
-    g.ep_ret += reward;
-    g.ep_len += 1;
-    if (done) {
-      if (ls == 0) {
-        MGN_G double* st = gs.epstats + (size_t)env * 4;
-        st[0] = g.ep_ret;
-        st[1] = g.ep_len;
-        st[2] = curEq;
-        g.n_done = g.n_done + 1;
-        st[3] = g.n_done;
-      }
-      g.ep_ret = 0;
-      g.ep_len = 0;
-    }
+    ep_account(g.ep_ret, g.ep_len, g.n_done, reward, done, curEq, ls == 0, gs.epstats + (size_t)env * 4);
   }
   if (p.W > 0) {
     // StackerDiscrete.stream_state of the State (preprocessor.py:172-175):
@@ -775,19 +735,15 @@ __global__ __launch_bounds__(DUO_BLOCK) void k_step_duo(KParams p, mgn_traj out,
     DuoRec<S>& rc = sh.rec[j & 1];
     if (ticking && s.valid[0]) s.P[0] = sh.price[l];
     if (stepping) {
-      // post-tick sums, equity, done (Env.h:211-223): only L*P sees the new prices
-      Sums q = sa;
-      {
-        double tlp[M];
-        tlp[0] = s.L[0] * s.P[0];
-        q.lp = canon<M, S>(tlp);
-      }
-      const double curEq = (cash + q.lp) - q.b;
-      // Env.h:211-212 (0.01 clamp for step(i, u), Env.h:238)
+      // post-tick sums, equity, reward, done (mgn_finish.h)
+      Sums q;
+      const double curEq = post_tick<M, S, false>(s.L, s.P, cash, sa.ml, sa.sh, sa.b, q);
+      // env_reward's statement (mgn_finish.h), written out: through the helper
+      // the discrete-action n-step instantiations allocate registers otherwise
       const double ratio = curEq / prevEq;
       const double clampv = (in_kind == IN_SINGLE) ? 0.01 : 0.3;
       const double reward = log_ratio((ratio < clampv) ? clampv : ratio);
-      const bool done = any_mc || margin_call(q, cash, p.mainM) || (curEq < 0.1 * p.init_cash);
+      const bool done = done_test(any_mc != 0, q, cash, curEq, p);
 #ifdef MGN_STAMPS
       const unsigned long long t_p2a = __builtin_amdgcn_s_memtime();
 #endif

@@ -21,6 +21,7 @@
 #include "../../include/madigan_amd.h"
 #include "mgn_broker.h"
 #include "mgn_consts.h"
+#include "mgn_finish.h"
 #include "mgn_lane.h"
 #include "mgn_math.h"
 #include "mgn_params.h"
@@ -256,8 +257,8 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
       ts = next_ts<M>(s, p, ts);
     }
     if (stepping) {
-      // ---- reward / done (Env.h:211-223).  Only the L*P sum sees the new
-      // prices; the ledger sums are the ones after the Broker.
+      // ---- reward / done (mgn_finish.h).  The post-tick sums are post_tick's
+      // statement written out (the ledger sums are the ones after the Broker).
       Sums q = sa;
       {
         double tlp[M];
@@ -266,9 +267,7 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
         q.lp = canon<M, S>(tlp);
       }
       const double curEq = (cash + q.lp) - q.b;
-      const double ratio = curEq / prevEq;
-      const double clampv = (in_kind == IN_SINGLE) ? 0.01 : 0.3;
-      const double reward = log_ratio((ratio < clampv) ? clampv : ratio);
+      const double reward = env_reward(curEq, prevEq, in_kind);
       int bad = 0;
       if constexpr (XCH) {
         bad = any_mc;  // every lane saw every round's risk
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
         for (int m = 0; m < M; ++m) bad |= (rk[m] != MGN_GREEN && rk[m] != MGN_INSUFF_MARGIN) ? 1 : 0;
         bad = seg_or<S>(bad);
       }
-      const bool done = bad || margin_call(q, cash, p.mainM) || (curEq < 0.1 * p.init_cash);
+      const bool done = done_test(bad != 0, q, cash, curEq, p);
 
       // ---- State.portfolio = ledgerNormedFull (Portfolio.cpp:150-155)
       const double port0 = (cash - q.b) / curEq;
@@ -285,7 +284,8 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
 #pragma unroll
       for (int m = 0; m < M; ++m) portA[m] = (s.L[m] * s.P[m]) / curEq;
 
-      // ---- agent-side per-asset reward (offpolicy_q.py:152-164)
+      // ---- agent-side per-asset reward (agent_ratio; the diagnostic bit 8
+      // skips its log)
       double ar[M];
 #pragma unroll
       for (int m = 0; m < M; ++m) {
@@ -293,12 +293,12 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
           ar[m] = 0.;
           continue;
         }
-        double v = (((s.L[m] * s.P[m]) - prevVal[m]) - (tu[m] * tp[m] + tc[m])) / prevEq;
-        v += 1;
-        v = (v < .35) ? .35 : v;
+        const double v = agent_ratio(s.L[m], s.P[m], prevVal[m], tu[m], tp[m], tc[m], prevEq);
         ar[m] = (p.ablate & 8) ? v : log_ratio(v);
       }
-      // ---- reward shaping
+      // ---- reward shaping.  PPC's term is ppc_cos's statement (mgn_finish.h)
+      // written out: through the helper the kernels of two and more slots per
+      // lane allocate registers otherwise
       double cos_term = 0.;
       if (p.shaper == MGN_SHAPER_PPC) {
         double pp[M], pq[M];
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
         // segment's fill count / oldest index, column owners touch the ring
         const int n = p.nstep;
         const int L1 = nlen + 1;
-        const int pops = done ? L1 : (L1 >= n ? 1 : 0);
+        const int pops = pop_count(done, L1, n);
         const bool ppc = p.shaper == MGN_SHAPER_PPC;
         double* row = (out.shaped && !(p.ablate & 4)) ? out.shaped + (oN + env) * (size_t)n * D : nullptr;
         if (D == 1) {
@@ -380,7 +380,9 @@ __global__ __launch_bounds__(BLOCK) void k_step(KParams p, mgn_traj out, int in_
         }
       }
 
-      // ---- episode statistics
+      // ---- episode statistics: ep_account's statement (mgn_finish.h) written
+      // out, the episode count kept in the row (through the helper the
+      // register allocation of this kernel changes)
       ep_ret += reward;
       ep_len += 1;
       if (done) {

@@ -325,17 +325,34 @@ __device__ __noinline__ double naive_n(int shaper, const double* ring, int n, in
   return clip1(s);
 }
 
+// update_parameters of DSR (nstep_buffer.py:86-91) and DDR (:157-162), after a
+// one-step reward or from the oldest entry of a pop: A += eta (r - A); B toward
+// r^2, DDR toward the downside square minimum(r, 0)^2 (a NaN passes through).
+// For these two shapers only: the caller guards.
+__device__ __forceinline__ void est_update(int shaper, double r, double& A, double& B, double eta) {
+  A += eta * (r - A);
+  if (shaper == MGN_SHAPER_DSR) {
+    B += eta * (r * r - B);
+  } else {
+    double m = r < 0. ? r : 0.;
+    if (r != r) m = r;
+    B += eta * (m * m - B);
+  }
+}
 // one shaper evaluation + parameter update, n = 1 (nstep_buffer.py:62-91, :128-162)
 __device__ __forceinline__ double shape(int shaper, double r, double& A, double& B, double eta,
                                         double cos_term, double ex) {
   if (shaper == MGN_SHAPER_DSR) {
     const double out = clip1((0.0 + 1.0 * dsr_one(r, A, B)) / 1);
-    A += eta * (r - A);
-    B += eta * (r * r - B);
+    est_update(MGN_SHAPER_DSR, r, A, B, eta);
     return out;
   }
   if (shaper == MGN_SHAPER_DDR) {
     const double out = clip1((0.0 + 1.0 * ddr_one(r, A, B)) / 1);
+    // est_update(MGN_SHAPER_DDR), written out with the downside formed first:
+    // the call's order (A first) moves instructions in k_step's and
+    // k_step_duo's one-step kernels, and k_step_duo's then run slower
+    // (profiles/finish_once_ab.json)
     double m = r < 0. ? r : 0.;
     if (r != r) m = r;
     A += eta * (r - A);
@@ -346,6 +363,28 @@ __device__ __forceinline__ double shape(int shaper, double r, double& A, double&
   if (shaper >= MGN_SHAPER_SHARPE) return naive1(shaper, r, ex);
   return r;
 }
+// shape() as the pipelined kernels evaluate the env's scalar column: DDR's
+// summand with its reward-independent operands formed ahead (ddr_one_pre, the
+// same operations on the same operands as ddr_one)
+__device__ __forceinline__ double shape_one(int shaper, double r, double& A, double& B, double eta,
+                                            double cos_term, double ex) {
+  if (shaper == MGN_SHAPER_DDR) {
+    const double out = clip1((0.0 + 1.0 * ddr_one_pre(r, A, B, ddr_pre(A, B))) / 1);
+    // est_update(MGN_SHAPER_DDR), written out as in shape() (a shape() with
+    // a flag for the summand also moves k_step_duo's code)
+    double m = r < 0. ? r : 0.;
+    if (r != r) m = r;
+    A += eta * (r - A);
+    B += eta * (m * m - B);
+    return out;
+  }
+  return shape(shaper, r, A, B, eta, cos_term, ex);
+}
+
+// NStepBuffer.add + pop_nstep_sarsd's pops of a step that finds L1 entries
+// (its own included) in a buffer of n (replay_buffer.py:68-80): every entry on
+// done, else one when the buffer is full
+__device__ __forceinline__ int pop_count(bool done, int L1, int n) { return done ? L1 : (L1 >= n ? 1 : 0); }
 
 // NStepBuffer.add + pop_nstep_sarsd for reward column d of one env
 // (nstep_buffer.py:315-356 as replay_buffer.py:68-80 drives it): append v; pop
@@ -384,15 +423,7 @@ __device__ __forceinline__ void nstep_column(const KParams& p, RingP ring, OutP 
     double res = acc;
     if (sr) {
       res = clip1(acc / len);
-      const double r0 = ring[(size_t)head * D + d];
-      A += p.eta * (r0 - A);
-      if (p.shaper == MGN_SHAPER_DSR) {
-        B += p.eta * (r0 * r0 - B);
-      } else {
-        double m = r0 < 0. ? r0 : 0.;
-        if (r0 != r0) m = r0;
-        B += p.eta * (m * m - B);
-      }
+      est_update(p.shaper, ring[(size_t)head * D + d], A, B, p.eta);
     }
     if (out) out[(size_t)pops * D + d] = res;
     head = (head + 1) % n;

@@ -53,6 +53,7 @@
 #include "mgn_broker.h"
 #include "mgn_consts.h"
 #include "mgn_diag.h"
+#include "mgn_finish.h"
 #include "mgn_gout.h"
 #include "mgn_lane.h"
 #include "mgn_math.h"
@@ -104,28 +105,6 @@ constexpr int kNstU = 3;
 __device__ __forceinline__ bool trio_exit(int j, int K, const int32_t& more) {
   if (j < K) return false;
   return !__builtin_amdgcn_readfirstlane(more);
-}
-
-// The done test of the step L ran in the previous iteration (Env.h:216-218),
-// on the records -- the ledger after the orders, the tick's prices, cash, the
-// price-independent sums and the refused-order flag.  The ONE definition:
-// the finish role's own test, and (one-step launches, TAIL_EXACT) the
-// generator's and the ledger's copies of it, which must agree with the
-// finish role's reset flag -- a term added here reaches all three.  q and
-// curEq: the post-tick sums and equity (the finish role's reward reads them)
-template <int M, int S, bool ONE>
-__device__ __forceinline__ bool rec_done(const double (&Lr)[M], const double (&P)[M], double cashv, double ml,
-                                         double shv, double b, bool any_mc, const KParams& p, Sums& q,
-                                         double& curEq) {
-  double tlp[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) tlp[m] = Lr[m] * P[m];
-  q.lp = canon<M, S, ONE>(tlp);
-  q.ml = ml;
-  q.sh = shv;
-  q.b = b;
-  curEq = (cashv + q.lp) - q.b;
-  return any_mc || margin_call(q, cashv, p.mainM) || (curEq < 0.1 * p.init_cash);
 }
 
 // TR_REFILL (WIN): the iteration's tick was an auto-reset refill tick
@@ -260,7 +239,8 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
   constexpr bool GLOG = WIN && !RP;
   constexpr int NPADS = 2;  // NST: ring, pop summands
   // NST == 2: the running-sum pop (MGN_NSTEP_POP_RUNNING, nrun_pop; the host
-  // routes only DSR / DDR / PPC / none here); NST == 1: the exact pop
+  // routes DSR / DDR / PPC / none here, and sortino_shaperB on the
+  // one-wave-per-role layouts: SBR below); NST == 1: the exact pop
   constexpr bool NRUN = NST == 2;
   // sortino_shaperB's running pop: the one-wave-per-role layouts only (the
   // windowed and small-batch handles, R1 among them); at 256 lanes its code
@@ -1263,9 +1243,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       const bool mine = ls < fcnt;  // the lane's entry: slot el S + ls = l
       const double curEq = mine ? s_fqc[l] : 1., prevEq = mine ? s_fqp[l] : 1.;
       const int k = s_fqk[l];
-      const double ratio = curEq / prevEq;
-      const double clampv = (in_kind == IN_SINGLE) ? 0.01 : 0.3;
-      const double reward = log_ratio((ratio < clampv) ? clampv : ratio);
+      const double reward = env_reward(curEq, prevEq, in_kind);
       double x = mine ? s_fqx[l] : 0.;
       asm volatile("" : "+v"(x));
       const double port0 = x / curEq;
@@ -1286,17 +1264,8 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
         }
         if (i < fcnt) {
           const double ri = r[i];
-          if (p.shaper == MGN_SHAPER_DDR) {
-            double m = ri < 0. ? ri : 0.;
-            if (ri != ri) m = ri;
-            g.shA += p.eta * (ri - g.shA);
-            g.shB += p.eta * (m * m - g.shB);
-          } else if (p.shaper == MGN_SHAPER_DSR) {
-            g.shA += p.eta * (ri - g.shA);
-            g.shB += p.eta * (ri * ri - g.shB);
-          }
-          ep_ret += ri;
-          ep_len += 1;
+          if (p.shaper == MGN_SHAPER_DDR || p.shaper == MGN_SHAPER_DSR) est_update(p.shaper, ri, g.shA, g.shB, p.eta);
+          ep_add(ep_ret, ep_len, ri);
           if ((fdone >> i) & 1) {
             st_ret = ep_ret;
             st_len = ep_len;
@@ -1307,7 +1276,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
           }
         }
       }
-      if (last >= 0 && ls == 0) {  // episode statistics
+      if (last >= 0 && ls == 0) {  // ep_account's row, of the batch's last episode end
         MGN_G double* st = gs.epstats + (size_t)env * 4;
         st[0] = st_ret;
         st[1] = st_len;
@@ -1396,7 +1365,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       }
       const double cashv = cashrec;
       const double prevEq = prevrec;
-      // post-tick sums, equity, done (rec_done, the one definition), reward
+      // post-tick sums, equity, done (rec_done, mgn_finish.h), reward
       // (Env.h:211-223)
       Sums q;
       double curEq;
@@ -1442,9 +1411,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
       } else {
       // (the per-step chain: every other handle of these instantiations, and
       // every other instantiation)
-      const double ratio = curEq / prevEq;
-      const double clampv = (in_kind == IN_SINGLE) ? 0.01 : 0.3;
-      const double reward = log_ratio((ratio < clampv) ? clampv : ratio);
+      const double reward = env_reward(curEq, prevEq, in_kind);
       if (j == 1) MGN_IT(56, 2 * TRIO_W);
       // ledgerNormedFull, agent reward, PPC, shaper (as k_step_duo's finish)
       double ar[M], portA[M];
@@ -1464,10 +1431,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
         ar[m] = 0.;
         if (f.valid[m] && need_ar) {
           const int x = lx + m;
-          double v = (((Lc * P) - sh.rPv[prv][x]) - (sh.rTu[prv][x] * sh.rTp[prv][x] + sh.rTc[prv][x])) / prevEq;
-          v += 1;
-          v = (v < .35) ? .35 : v;
-          ar[m] = log_ratio(v);
+          ar[m] = agent_reward(Lc, P, sh.rPv[prv][x], sh.rTu[prv][x], sh.rTp[prv][x], sh.rTc[prv][x], prevEq);
         }
         portA[m] = 0.;
         if (need_pa) {
@@ -1477,19 +1441,8 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
         }
       }
       double cos_term = 0.;
-      if (p.shaper == MGN_SHAPER_PPC) {
-        double pp[M], pq[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-          const double qv = f.valid[m] ? s_tgt[1 + f.asset[m]] : 0.;
-          const double pv = f.valid[m] ? portA[m] : 0.;
-          pp[m] = pv * pv;
-          pq[m] = pv * qv;
-        }
-        const double np_ = sqrt(port0 * port0 + canon<M, S, ONE>(pp));
-        const double dot = port0 * s_tgt[0] + canon<M, S, ONE>(pq);
-        cos_term = p.cos_temp * (dot / (np_ * g.cos_qn));
-      }
+      if (p.shaper == MGN_SHAPER_PPC)
+        cos_term = ppc_cos<M, S, ONE>(f.valid, f.asset, port0, portA, s_tgt, p.cos_temp, g.cos_qn);
       double shaped_s = 0., rin_s = 0., shaped_v = 0.;
       int pops = 1;
       MGN_ST(Tf1 = __builtin_amdgcn_s_memtime();)
@@ -1504,7 +1457,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
         double* scr = ring + nst_pad(n, S);
         const double v = (p.shaper == MGN_SHAPER_PPC) ? rin_s + cos_term : rin_s;
         const int L1 = nlen + 1;
-        pops = done ? L1 : (L1 >= n ? 1 : 0);
+        pops = done ? L1 : (L1 >= n ? 1 : 0);  // pop_count (mgn_shapers.h), written out
         MGN_G double* row = (om & O_SHP) ? ov.shaped + kidx(k, sN, (size_t)env) * (size_t)n : nullptr;
         // append v; then the pops (one when the buffer is full, every entry
         // on done), each by all the env's lanes: summand kk on lane kk mod S
@@ -1542,8 +1495,9 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
               acc += sortinoB_term(ring[idx], s_disc[kk], p.sexp);
             return clip1(acc);
           };
-          // one pop: the shaper state steps (update_parameters, exact), the
-          // oldest entry leaves the sums
+          // one pop: the shaper state steps (update_parameters, exact:
+          // est_update, mgn_shapers.h, written out), the oldest entry leaves
+          // the sums
           const auto pop_done = [&](int pj, double res, double r0, double rt0) {
             if (p.shaper == MGN_SHAPER_DSR || p.shaper == MGN_SHAPER_DDR) {
               g.shA += p.eta * (r0 - g.shA);
@@ -1612,7 +1566,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
           if (p.shaper == MGN_SHAPER_SORTINO_B) res = clip1(acc);  // (naive_n, len > 1)
           if (p.shaper == MGN_SHAPER_DSR || p.shaper == MGN_SHAPER_DDR) {
             res = clip1(acc / len);
-            const double r0 = ring[head];
+            const double r0 = ring[head];  // est_update, written out
             g.shA += p.eta * (r0 - g.shA);
             if (p.shaper == MGN_SHAPER_DSR) {
               g.shB += p.eta * (r0 * r0 - g.shB);
@@ -1634,16 +1588,7 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
         nlen = L1 - pops;
       } else if (D == 1) {
         rin_s = (p.reward_mode == MGN_REWARD_AGENT_SUM) ? canon<M, S, ONE>(ar) : reward;
-        if (p.shaper == MGN_SHAPER_DDR) {  // shape() for DDR (nstep_buffer.py:128-162)
-          const double r = rin_s;
-          shaped_s = clip1((0.0 + 1.0 * ddr_one_pre(r, g.shA, g.shB, ddr_pre(g.shA, g.shB))) / 1);
-          double m = r < 0. ? r : 0.;
-          if (r != r) m = r;
-          g.shA += p.eta * (r - g.shA);
-          g.shB += p.eta * (m * m - g.shB);
-        } else {
-          shaped_s = shape(p.shaper, rin_s, g.shA, g.shB, p.eta, cos_term, p.sexp);
-        }
+        shaped_s = shape_one(p.shaper, rin_s, g.shA, g.shB, p.eta, cos_term, p.sexp);
       } else {
         shaped_v = f.valid[0] ? shape(p.shaper, ar[0], g.shA, g.shB, p.eta, cos_term, p.sexp) : 0.;  // M = 1
       }
@@ -1691,24 +1636,10 @@ __global__ __launch_bounds__(3 * TW, 1) void k_step_trio(
           rhead = p.W - 1;
         }
       }
-      // episode statistics
-      ep_ret += reward;
-      ep_len += 1;
-      if (done) {
-        if (ls == 0) {
-          MGN_G double* st = gs.epstats + (size_t)env * 4;
-          st[0] = ep_ret;
-          st[1] = ep_len;
-          st[2] = curEq;
-          n_done = n_done + 1;
-          st[3] = n_done;
-        }
-        ep_ret = 0;
-        ep_len = 0;
-        if (p.auto_reset) {
-          rst_out = 1;
-          tail_rst = TAIL && K == 1;
-        }
+      ep_account(ep_ret, ep_len, n_done, reward, done, curEq, ls == 0, gs.epstats + (size_t)env * 4);
+      if (done && p.auto_reset) {
+        rst_out = 1;
+        tail_rst = TAIL && K == 1;
       }
       }
     }
