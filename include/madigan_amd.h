@@ -49,6 +49,10 @@
  *                     prefix-sum sampling and the priority update
  *                     (madigan/utils/buffers/prioritized_replay_buffer.py:13-87,
  *                     segment_tree.py:7-66)
+ *   mgn_prep_state    the network-ready state: prep_state_tensors /
+ *   mgn_ring_prep     prep_sarsd_tensors of every agent (madigan/modelling/
+ *   mgn_rollout_prep  algorithm/dqn.py:188-213, ddpg.py:215-246, sac.py:237-265,
+ *   mgn_prep_xbuf_*   dqn_recurrent.py:202-227; abs_port_norm utils.py:31-41)
  *   mgn_tear_*        the test episode's record and its tearsheet
  *                     (madigan/utils/metrics.py:83-175 test_summary;
  *                     offpolicy_q.py:254-274 test_episode)
@@ -447,6 +451,40 @@ enum {
   MGN_PBUF_SEAT_WRITTEN = 1  /* the slot the transition went to */
 };
 
+/* Network-ready states (prep_state_tensors / prep_sarsd_tensors of the agents,
+ * dqn.py:188-213, ddpg.py:215-246, sac.py:237-265, dqn_recurrent.py:202-227):
+ * the reference's preparation applied to what mgn_window / a sampled batch
+ * hold, zero padding included.  New symbols only: MGN_ABI_VERSION stays 11.
+ *   price (..., W, F) float32: every float64 element of the window (under the
+ *         ring's normaliser) rounded once to nearest float32; a copy from
+ *         float32 slot storage
+ *   port  (..., A+1) float32: row W - 1 of the portfolio window -- the zero
+ *         padding while the window is not full.  MGN_PORT_NORM_NONE (DDPG): the
+ *         row rounded once.  MGN_PORT_NORM_ABS (abs_port_norm, modelling/
+ *         algorithm/utils.py:31-41; DQN, IQN, SAC): in float64
+ *         s = ((|p0| + |p1|) + ...) + |pA| in index order, q_j = p_j / s an
+ *         IEEE quotient, q_j rounded once; s = 0 gives NaN as the reference's
+ *         0 / 0 does (a padding row, a batch row of idx = -1)
+ *   ts    (...) int64: entry W - 1 of the timestamp window */
+enum { MGN_PORT_NORM_NONE = 0, MGN_PORT_NORM_ABS = 1 };
+
+/* a prepared SARSD batch, caller-owned device memory: state_price / next_price
+ * (B, W, F), state_port / next_port (B, A+1), state_ts / next_ts (B) as above;
+ * action (B, A) int64 as mgn_xbuf_batch's (a weights buffer's float rows come
+ * from mgn_xbuf_gather_wact by idx); reward (B, D) float32 rounded once from
+ * float64; done (B) 0 / 1; idx (B) int64, the slot of each row (-1: none, a
+ * row of zeros).  Any pointer may be NULL. */
+typedef struct {
+  float *state_price, *state_port;
+  int64_t *state_ts;
+  float *next_price, *next_port;
+  int64_t *next_ts;
+  int64_t *action;
+  float *reward;
+  uint8_t *done;
+  int64_t *idx;
+} mgn_xbuf_prep_batch;
+
 typedef struct mgn_env mgn_env;
 
 int mgn_abi_version(void);
@@ -724,6 +762,39 @@ int mgn_pbuf_sample(const mgn_xbuf *xbuf, mgn_pbuf *pbuf, const mgn_xbuf_batch *
  * Clears the cache.  MGN_ERR_CONFIG: a bad xbuf or pbuf, a null pa_dev, no
  * cached batch, n_batch != cached_len. */
 int mgn_pbuf_update(const mgn_xbuf *xbuf, mgn_pbuf *pbuf, const double *pa_dev, int64_t n_batch, void *stream);
+/* prep_state_tensors(StackerDiscrete.current_data()) (dqn.py:188-195,
+ * ddpg.py:215-222, sac.py:237-244) straight from the ring: price (N, W,
+ * n_price) float32 under the ring's normaliser (out_stride / out_offset as
+ * mgn_ring_gather), port (N, n_port) float32 under port_norm (MGN_PORT_NORM_*),
+ * ts (N) int64 -- see mgn_xbuf_prep_batch's comment.  price equals
+ * mgn_ring_gather's rounded to float32 bit for bit; the portfolio and timestamp
+ * windows are not materialised.  Any output may be NULL.  Runs on `stream`,
+ * does not synchronise the host.  mgn_ring_prep_plan reports the launch's
+ * geometry: the envs one workgroup owns and whether their rows go through LDS. */
+int mgn_ring_prep(const mgn_ring *ring, float *price_dev, float *port_dev, int64_t *ts_dev, int32_t port_norm,
+                  void *stream);
+int mgn_ring_prep_plan(const mgn_ring *ring, int32_t *envs_per_group_out, int32_t *staged_out);
+/* the same of the handle's ring on the handle's stream (price (N, W, F), port
+ * (N, A+1), ts (N); any may be NULL), and the agent loop's one call per step
+ * (offpolicy_q.py:143, :193-194 then dqn.py:188-195): mgn_rollout, then
+ * mgn_prep_state -- the prepared twin of mgn_rollout_window */
+int mgn_prep_state(mgn_env *env, float *price_dev, float *port_dev, int64_t *ts_dev, int32_t port_norm);
+int mgn_rollout_prep(mgn_env *env, const int8_t *actions_dev, int32_t k_steps, const mgn_traj *out,
+                     float *price_dev, float *port_dev, int64_t *ts_dev, int32_t port_norm);
+/* prep_sarsd_tensors(buffer.sample(B)) (dqn.py:197-213, ddpg.py:224-246,
+ * sac.py:246-265): mgn_xbuf_sample / mgn_xbuf_gather / mgn_pbuf_sample with
+ * the prepared batch in place of the collated one -- the same indices for the
+ * same seed and call (the same injected uniforms, cached indices and weights
+ * for the prioritized draw, so mgn_pbuf_update follows as after
+ * mgn_pbuf_sample), each row the preparation of the row those return.
+ * MGN_ERR_CONFIG as their counterparts, and for an unknown port_norm. */
+int mgn_prep_xbuf_sample(const mgn_xbuf *xbuf, const mgn_xbuf_prep_batch *batch, int64_t n_batch,
+                         int32_t port_norm, uint64_t seed, uint64_t call, void *stream);
+int mgn_prep_xbuf_gather(const mgn_xbuf *xbuf, const int64_t *idx_dev, const mgn_xbuf_prep_batch *batch,
+                         int64_t n_batch, int32_t port_norm, void *stream);
+int mgn_prep_pbuf_sample(const mgn_xbuf *xbuf, mgn_pbuf *pbuf, const mgn_xbuf_prep_batch *batch,
+                         float *weights_dev, int64_t n_batch, int32_t port_norm, double beta, uint64_t seed,
+                         uint64_t call, void *stream);
 /* Lane layout of the step kernels: assets held per lane (1, 2, 4, 8; 0 =
  * automatic, the default).  Results are bit-identical for every layout (the
  * canonical reduction tree does not depend on it); only speed changes. */

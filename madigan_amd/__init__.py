@@ -14,6 +14,7 @@ from .env import (Asset, BatchedEnv, BrokerResponse, DataSourceTick, Env, EnvInf
                   get_env_info, make_batched_env, make_env)
 from .hdf import HDFSourceSingle, write_hdf
 from .metrics import EpisodeRecorder, make_timeframes
+from .prepared import PORT_NORMS
 from .replay_buffer import DeviceReplayBuffer
 from .prioritized_replay_buffer import DevicePrioritizedReplayBuffer, make_buffer_from_config
 from .preprocessor import (MultiStackerDiscrete, PreProcessor, StackerDiscrete, StackerDiscretePairs,
@@ -21,7 +22,7 @@ from .preprocessor import (MultiStackerDiscrete, PreProcessor, StackerDiscrete, 
 
 __all__ = ["Asset", "BatchedEnv", "BrokerResponse", "ConfigError", "DataSourceTick", "DevicePrioritizedReplayBuffer",
            "DeviceReplayBuffer", "Env",
-           "EnvInfo", "EpisodeRecorder", "HDFSourceSingle", "PreProcessor", "RiskInfo", "SourceSpec",
+           "EnvInfo", "EpisodeRecorder", "HDFSourceSingle", "PORT_NORMS", "PreProcessor", "RiskInfo", "SourceSpec",
            "StackerDiscrete", "State", "get_env_info", "make_batched_env", "make_buffer_from_config", "make_env",
            "make_preprocessor", "make_timeframes", "MultiStackerDiscrete", "StackerDiscretePairs",
            "StackerDiscreteReturns", "replay_spec", "spec_from_config", "write_hdf"]

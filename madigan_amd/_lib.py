@@ -145,6 +145,7 @@ class PBuf(C.Structure):  # mgn_pbuf
 
 
 PBUF_SEAT_NEXT, PBUF_SEAT_WRITTEN = 0, 1
+PORT_NORM_NONE, PORT_NORM_ABS = 0, 1  # MGN_PORT_NORM_*
 
 SYMBOLS = {
     # name: (restype, argtypes)
@@ -205,6 +206,17 @@ SYMBOLS = {
     "mgn_pbuf_sample": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.POINTER(XBufBatch), C.c_void_p, C.c_int64,
                                   C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
     "mgn_pbuf_update": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.c_void_p, C.c_int64, C.c_void_p]),
+    # network-ready states (mgn_prep.hip); the batch struct's mirror is prepared.XBufPrepBatch
+    "mgn_ring_prep": (C.c_int, [C.POINTER(Ring), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mgn_ring_prep_plan": (C.c_int, [C.POINTER(Ring), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgn_prep_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "mgn_rollout_prep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Traj), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int32]),
+    "mgn_prep_xbuf_sample": (C.c_int, [C.POINTER(XBuf), C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                       C.c_void_p]),
+    "mgn_prep_xbuf_gather": (C.c_int, [C.POINTER(XBuf), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "mgn_prep_pbuf_sample": (C.c_int, [C.POINTER(XBuf), C.POINTER(PBuf), C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
     "mgn_set_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "mgn_get_layout": (C.c_int, [C.c_void_p]),
     "mgn_set_schedule": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -4,7 +4,7 @@
 
 Translation units: mgn_api.hip (the handle's C ABI, window/action kernels),
 one unit per descriptor subject with its kernels and its entry points
-(mgn_rnorm.hip, mgn_tear.hip, mgn_xbuf.hip, mgn_pbuf.hip), plus one
+(mgn_rnorm.hip, mgn_tear.hip, mgn_xbuf.hip, mgn_pbuf.hip, mgn_prep.hip), plus one
 mgn_launch_a<APAD>.hip per padded asset count with that APAD's (M, S)
 instantiations of the step kernels (and mgn_launch_a<APAD>w.hip with its
 portfolio-weight instantiations); they compile in parallel and link into

@@ -856,6 +856,26 @@ int mgn_rollout_window(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, c
   return st != MGN_OK ? st : mgn_window(e, price_dev, port_dev, ts_dev);
 }
 
+// prep_state_tensors of the handle's ring (k_ring_prep, mgn_prep.hip)
+int mgn_prep_state(mgn_env* e, float* price_dev, float* port_dev, int64_t* ts_dev, int32_t port_norm) {
+  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
+  if (e->W == 0) return fail(e, MGN_ERR_CONFIG, "handle has no window (window_length = 0)");
+  if (port_norm != MGN_PORT_NORM_NONE && port_norm != MGN_PORT_NORM_ABS)
+    return fail(e, MGN_ERR_CONFIG, "mgn_prep_state: port_norm must be MGN_PORT_NORM_NONE or MGN_PORT_NORM_ABS");
+  return check_hip(e, (hipError_t)mgn::prep_launch_ring(ring_desc(e), price_dev, port_dev, ts_dev, port_norm, e->stream),
+                   "mgn_prep_state");
+}
+
+int mgn_rollout_prep(mgn_env* e, const int8_t* actions_dev, int32_t k_steps, const mgn_traj* out, float* price_dev,
+                     float* port_dev, int64_t* ts_dev, int32_t port_norm) {
+  if (!e) return fail(nullptr, MGN_ERR_ARG, "null handle");
+  if (e->W == 0) return fail(e, MGN_ERR_CONFIG, "handle has no window (window_length = 0)");
+  if (port_norm != MGN_PORT_NORM_NONE && port_norm != MGN_PORT_NORM_ABS)
+    return fail(e, MGN_ERR_CONFIG, "mgn_rollout_prep: port_norm must be MGN_PORT_NORM_NONE or MGN_PORT_NORM_ABS");
+  const int st = mgn_rollout(e, actions_dev, k_steps, out);
+  return st != MGN_OK ? st : mgn_prep_state(e, price_dev, port_dev, ts_dev, port_norm);
+}
+
 int mgn_generate_actions(mgn_env* e, int8_t* actions_dev, int32_t k_steps, uint64_t seed) {
   if (!e || !actions_dev) return fail(e, MGN_ERR_ARG, "null handle/actions");
   if (k_steps < 1) return fail(e, MGN_ERR_LENGTH, "k_steps must be >= 1");
@@ -913,30 +933,8 @@ int mgn_set_broker(mgn_env* e, double required_margin, double maintenance_margin
   return MGN_OK;
 }
 
-static mgn::RingDesc ring_from(const mgn_ring* r) {
-  mgn::RingDesc d;
-  d.N = r->n_envs; d.F = r->n_price; d.Pn = r->n_port; d.W = r->window; d.norm = r->norm_type;
-  d.prelog = 0;
-  d.transform = r->transform;
-  d.ostride = r->out_stride > 0 ? r->out_stride : r->n_price;
-  d.ooff = r->out_offset;
-  d.ring = r->ring; d.ring_ts = r->ring_ts; d.head = r->head; d.len = r->len;
-  return d;
-}
-
-static int ring_ok(const mgn_ring* r) {
-  if (!r || !r->ring || !r->ring_ts || !r->head || !r->len) return fail(nullptr, MGN_ERR_ARG, "null ring buffers");
-  // n_price >= 1: the gather kernels write the timestamps from price column 0
-  if (r->n_envs < 1 || r->window < 1 || r->n_price < 1 || r->n_port < 0)
-    return fail(nullptr, MGN_ERR_LENGTH, "bad ring dimensions");
-  if (r->norm_type < 0 || r->norm_type > MGN_NORM_LOG_STANDARD_NORMAL)
-    return fail(nullptr, MGN_ERR_CONFIG, "unknown norm_type");
-  if (r->transform != MGN_RING_PLAIN && !(r->transform == MGN_RING_PAIR_RATIO && r->n_price == 1))
-    return fail(nullptr, MGN_ERR_CONFIG, "ring transform PAIR_RATIO stores one price column");
-  if (r->out_offset < 0 || (r->out_stride > 0 && r->out_offset + r->n_price > r->out_stride))
-    return fail(nullptr, MGN_ERR_LENGTH, "gathered price columns exceed out_stride");
-  return MGN_OK;
-}
+using mgn::ring_from;  // mgn_ring.h
+using mgn::ring_ok;
 
 int mgn_ring_push(const mgn_ring* r, const double* price_dev, const double* port_dev,
                   const uint64_t* ts_dev, void* stream) {

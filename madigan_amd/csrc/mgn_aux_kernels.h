@@ -11,22 +11,14 @@
 #include "mgn_math.h"
 #include "mgn_params.h"
 #include "mgn_reduce.h"
+#include "mgn_ring.h"
 
 namespace mgn {
 
 // ---------------------------------------------------------------------------
 // Window kernels (StackerDiscrete, preprocessor.py:143-199).  Ring layout
-// (N, W, C) with C = F + P columns (price features then portfolio entries).
-struct RingDesc {
-  int N, F, Pn, W, norm;
-  int prelog;  // norm "log" already applied to the price columns at push
-  int transform;  // MGN_RING_PAIR_RATIO: pushed price rows have 2 columns, stored p0 / p1
-  int ostride, ooff;  // gathered price: row stride and first column in the output
-  double* ring;
-  uint64_t* ring_ts;
-  int32_t* head;
-  int32_t* len;
-};
+// (N, W, C) with C = F + P columns (price features then portfolio entries);
+// RingDesc is mgn_ring.h's.
 
 // stream_state: one thread per env (rare; the fused step writes its own rows)
 __global__ void k_ring_push(RingDesc r, const double* __restrict__ price,
@@ -61,13 +53,7 @@ __global__ void k_ring_clear(RingDesc r, const uint8_t* __restrict__ mask) {
 // current_data: one thread per (env, column); rows oldest -> newest, norm on
 // price columns (log_norm :79-81, lookback :63-66, standard_norm :83-92,
 // log_standard_norm :95-107: log without the clamp, nan-skipping mean / std).
-__device__ __forceinline__ double nan_to_num(double v) {
-  if (v != v) return 0.;
-  if (v == __builtin_inf()) return 1.7976931348623157e308;
-  if (v == -__builtin_inf()) return -1.7976931348623157e308;
-  return v;
-}
-
+// (nan_to_num: mgn_ring.h)
 __global__ __launch_bounds__(BLOCK) void k_ring_gather(RingDesc r, double* __restrict__ price_out,
                                                        double* __restrict__ port_out,
                                                        uint64_t* __restrict__ ts_out) {

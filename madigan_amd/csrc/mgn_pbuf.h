@@ -162,6 +162,12 @@ MGN_XB_HD int64_t pb_sample_index(const double* tree_sum, int64_t ts, double tot
   return idx >= 0 && idx < filled ? idx : -1;
 }
 
+// mgn_pbuf.hip, for mgn_prep.hip: the draw of mgn_pbuf_sample without its
+// gather (checks, indices into cached_idx, weights); an MGN_* status, refusals
+// recorded under the entry point's name `what`
+int pbuf_draw(const mgn_xbuf* x, mgn_pbuf* p, float* weights_dev, int64_t n_batch, double beta, uint64_t seed,
+              uint64_t call, void* stream, const char* what);
+
 }  // namespace mgn
 
 #endif  // MGN_PBUF_H_

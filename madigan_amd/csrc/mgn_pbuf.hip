@@ -169,6 +169,26 @@ int pbuf_ok(const mgn_xbuf* x, const mgn_pbuf* p) {
 }
 
 }  // namespace
+
+// the draw of a prioritized sample on its own, for mgn_prep_pbuf_sample
+// (mgn_prep.hip): mgn_pbuf_sample's checks and k_pbuf_draw launch -- the
+// indices into cached_idx (cached_len = n_batch), the weights -- without its
+// gather
+int pbuf_draw(const mgn_xbuf* x, mgn_pbuf* p, float* weights_dev, int64_t n_batch, double beta, uint64_t seed,
+              uint64_t call, void* stream, const char* what) {
+  int rc = pbuf_ok(x, p);
+  if (rc != MGN_OK) return rc;
+  if (!weights_dev) return fail(nullptr, MGN_ERR_CONFIG, std::string(what) + ": null weights");
+  if (n_batch < 1 || n_batch > p->cached_cap)
+    return fail(nullptr, MGN_ERR_CONFIG, std::string(what) + ": n_batch must be 1..cached_cap");
+  const unsigned grid = (unsigned)((n_batch + PB_DRAW_BLOCK - 1) / PB_DRAW_BLOCK);
+  hipLaunchKernelGGL(k_pbuf_draw, dim3(grid), dim3(PB_DRAW_BLOCK), 0, (hipStream_t)stream, *x, *p, weights_dev,
+                     n_batch, beta, seed, call);
+  rc = check_hip(nullptr, hipGetLastError(), what);
+  if (rc == MGN_OK) p->cached_len = n_batch;
+  return rc;
+}
+
 }  // namespace mgn
 
 using namespace mgn;

@@ -749,6 +749,60 @@ class BatchedEnv:
                                             *ptrs, int(per_step)), self.h)
         return out, win
 
+    def _prep_out(self, out):
+        """(price, port, ts) float32 / float32 / int64 buffers of a prepared
+        state and their pointers: ``out`` a triple of contiguous device
+        tensors (an entry None: that output is not written), or None for the
+        handle's own buffers, allocated once and overwritten by every call."""
+        torch = _torch()
+        want = (((self.N, self.W, self.F), torch.float32), ((self.N, self.A + 1), torch.float32),
+                ((self.N,), torch.int64))
+        if out is None:
+            if getattr(self, "_prep_bufs", None) is None:
+                self._prep_bufs = tuple(torch.empty(s, dtype=dt, device=self.device) for s, dt in want)
+            out = self._prep_bufs
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError("out must be (price, port, ts)")
+        for t, (shape, dt), name in zip(out, want, ("price", "port", "ts")):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or t.device != self.device
+                                  or not t.is_contiguous()):
+                raise ValueError(f"out {name} must be a contiguous {shape} {dt} tensor on {self.device}")
+        return out, [None if t is None else C.c_void_p(t.data_ptr()) for t in out]
+
+    def policy_state(self, port_norm: str = "abs", out=None):
+        """The agents' prep_state_tensors(preprocessor.current_data())
+        (dqn.py:188-195, ddpg.py:215-222) straight from the handle's ring
+        (mgn_prep_state): ``price`` (N, W, F) float32 = ``window()[0]`` rounded
+        once, ``port`` (N, A+1) float32 = the last row of ``window()[1]`` under
+        ``port_norm`` ("abs": abs_port_norm; "none": DDPG's plain row),
+        ``ts`` (N,) int64 = ``window()[2][:, -1]``; see ``madigan_amd.prepared``.
+        No host synchronisation; the portfolio and timestamp windows are not
+        written."""
+        from .prepared import port_norm_code
+        if not self.W:
+            raise RuntimeError("env built with window=0")
+        out, ptrs = self._prep_out(out)
+        L.check(self.lib.mgn_prep_state(self.h, *ptrs, port_norm_code(port_norm)), self.h)
+        return out
+
+    def rollout_policy_state(self, actions, out: Optional[dict] = None, port_norm: str = "abs", state_out=None):
+        """`rollout(actions, out)` then `policy_state(port_norm)` in one native
+        call (mgn_rollout_prep), the agent loop's call per step.  Returns the
+        trajectory and (price, port, ts)."""
+        from .prepared import port_norm_code
+        if not self.W:
+            raise RuntimeError("env built with window=0")
+        actions = self.launch_actions(actions)
+        K = int(actions.shape[0])
+        own = out is None
+        out = self.alloc_traj(K) if own else out
+        t = self._traj_for(out, K, cache=not own)
+        state, ptrs = self._prep_out(state_out)
+        L.check(self.lib.mgn_rollout_prep(self.h, C.c_void_p(actions.data_ptr()), K, C.byref(t), *ptrs,
+                                          port_norm_code(port_norm)), self.h)
+        return out, state
+
     def rollout_hist(self, actions, out: Optional[dict] = None) -> dict:
         """`rollout(actions)` that also keeps every ring push of the launch in
         the handle's launch history (mgn_rollout_hist), for `window_hist_view()`

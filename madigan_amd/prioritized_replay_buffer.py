@@ -156,6 +156,28 @@ class DevicePrioritizedReplayBuffer(DeviceReplayBuffer):
         self.sample_calls += 1
         return self._sarsd(t), w
 
+    def sample_prepared(self, n: int, port_norm=None):
+        """``sample(n)`` with the network-ready batch of
+        ``DeviceReplayBuffer.sample_prepared`` in place of the collated one
+        (mgn_prep_pbuf_sample): the same draw, cached indices and weights, so
+        ``update_priority`` follows as after ``sample``."""
+        torch = self.torch
+        n = int(n)
+        if n < 1:
+            raise ValueError("sample size must be >= 1")
+        if self._uniforms is not None and self._uniforms.numel() < n:
+            raise ValueError("fewer injected uniforms than rows")
+        code = self._prep_norm(port_norm)
+        self.beta = min(1., self.beta + self.beta_diff)
+        self._cache_for(n)
+        t, b = self._prep_batch(n)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            w = torch.empty(n, dtype=torch.float32, device=self.device)
+        L.check(self.lib.mgn_prep_pbuf_sample(C.byref(self._d), C.byref(self._p), C.byref(b), C.c_void_p(w.data_ptr()),
+                                              n, code, float(self.beta), self.seed, self.sample_calls, self._sp()))
+        self.sample_calls += 1
+        return self._sarsd(t), w
+
     # ---- priorities -----------------------------------------------------------
     def _calc_pa(self, td_error):
         """prioritized_replay_buffer.py:85-87, on the device tensor."""

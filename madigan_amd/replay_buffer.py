@@ -331,6 +331,65 @@ class DeviceReplayBuffer:
                                              int(idx.numel()), self._sp()))
         return self._sarsd(t)
 
+    # ---- network-ready batches (madigan_amd.prepared) ---------------------------
+    def _prep_norm(self, port_norm) -> int:
+        """None: the reference agent's choice for the buffer's kind -- "abs"
+        for discrete actions (DQN, dqn.py:197-213), "none" for portfolio
+        weights (DDPG, ddpg.py:224-246)."""
+        from .prepared import port_norm_code
+        if port_norm is None:
+            port_norm = "none" if self.action_kind == "weights" else "abs"
+        return port_norm_code(port_norm)
+
+    def _prep_batch(self, B: int):
+        from .prepared import XBufPrepBatch
+        torch = self.torch
+        W, F, A, D, f32, i64 = self.W, self.F, self.A, self.D, torch.float32, torch.int64
+        shapes = dict(state_price=((B, W, F), f32), state_port=((B, A + 1), f32), state_ts=((B,), i64),
+                      next_price=((B, W, F), f32), next_port=((B, A + 1), f32), next_ts=((B,), i64),
+                      action=((B, A), i64), reward=((B, D), f32), done=((B,), torch.uint8), idx=((B,), i64))
+        if self._wa is not None:  # filled by mgn_xbuf_gather_wact from idx (_sarsd)
+            shapes["action"] = ((B, A + 1), self.action_dtype)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            t = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in shapes.items()}
+        b = XBufPrepBatch()
+        if B:
+            for k, v in t.items():
+                if k != "action" or self._wa is None:
+                    setattr(b, k, v.data_ptr())
+        return t, b
+
+    def sample_prepared(self, n: int, port_norm=None):
+        """prep_sarsd_tensors(self.sample(n)) (dqn.py:197-213, ddpg.py:224-246)
+        in the gather itself (mgn_prep_xbuf_sample): (batch, None) with the
+        indices ``sample(n)`` would draw at this call.  ``state`` /
+        ``next_state`` are State(price (n, W, F) float32, portfolio (n, A+1)
+        float32 -- the window's last row under ``port_norm`` --, timestamp
+        (n,) int64), ``reward`` float32, ``done`` bool, ``action`` as
+        ``sample``'s; see ``madigan_amd.prepared``.  ``port_norm`` None: "abs"
+        for a discrete buffer, "none" for a weights buffer."""
+        if int(n) < 1:
+            raise ValueError("sample size must be >= 1")
+        code = self._prep_norm(port_norm)
+        t, b = self._prep_batch(int(n))
+        L.check(self.lib.mgn_prep_xbuf_sample(C.byref(self._d), C.byref(b), int(n), code, self.seed,
+                                              self.sample_calls, self._sp()))
+        self.sample_calls += 1
+        return self._sarsd(t), None
+
+    def sample_idx_prepared(self, idx, port_norm=None):
+        """prep_sarsd_tensors(self.sample_idx(idx)) (mgn_prep_xbuf_gather):
+        (batch, None); a row of idx = -1 is zeros, and NaN ``portfolio`` under
+        "abs" (the reference's 0 / 0)."""
+        torch = self.torch
+        code = self._prep_norm(port_norm)
+        idx = torch.as_tensor(idx).to(self.device, torch.int64).contiguous().view(-1)
+        t, b = self._prep_batch(int(idx.numel()))
+        if idx.numel():
+            L.check(self.lib.mgn_prep_xbuf_gather(C.byref(self._d), C.c_void_p(idx.data_ptr()), C.byref(b),
+                                                  int(idx.numel()), code, self._sp()))
+        return self._sarsd(t), None
+
     def get_full(self):
         return self.sample_idx(self.torch.arange(len(self), device=self.device))
 
